@@ -16,9 +16,13 @@ prefix with three RCCL all-to-alls per batch over xGMI (hdrf_amd/node.py).  Work
 fixed as N grows: scaling is weak.  (HDRF_BENCH_SAME_DEVICE=1 puts every rank on cuda:0 over gloo:
 a one-GPU rehearsal of the multi-rank path, not a measurement.)
 
-The line also carries the dominant kernel's roofline (HIP events on the library's stream)
-and the CPU oracle timed on this host on a bounded sample of the same corpus, whose
-per-block storeSize must equal the GPU's (bit-exact dedup ratio check).
+A plain run sets up, warms up, times the steps and prints the line, which also carries the
+dominant kernel's roofline (HIP events on the library's streams during the timed steps).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.  `--full` adds
+every measurement and check that takes a run of its own: the short config-4 / config-5 lines
+(child processes), the untimed serial pass (per-kernel "alone" rooflines), the CPU oracle timed on
+this host on a bounded sample of the same corpus, whose per-block storeSize must equal the GPU's,
+the whole-corpus storeSize check (bit-exact dedup ratio) and config 5's raw link probe.
 """
 import argparse
 import json
@@ -126,14 +130,24 @@ def parse():
     ap.add_argument("--seg-mib", type=int, default=1)
     ap.add_argument("--dup-ppm", type=int, default=500000)
     ap.add_argument("--seed", type=int, default=20251015)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the config-4 / config-5 sub-lines, the "
+                         "untimed serial pass (alone rooflines), the CPU baseline and chunk check, the whole-corpus "
+                         "storeSize check and config 5's link probe (each can still be turned off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64): every block's chunk count and storeSize, the stats, "
+                         "the allocator, and the per-chunk results of a fixed sample of the last batch's blocks")
     ap.add_argument("--index-log2", type=int, default=27)
     ap.add_argument("--hasher", type=int, default=0)
     ap.add_argument("--cpu-sample-blocks", type=int, default=0,
                     help="blocks of the CPU baseline sample (default: the first batch, checked chunk by chunk)")
     ap.add_argument("--no-cpu", action="store_true",
-                    help="no CPU leg: neither the timed baseline sample nor the whole-corpus storeSize check")
+                    help="--full without the CPU leg: neither the timed baseline sample nor the whole-corpus "
+                         "storeSize check")
     ap.add_argument("--no-corpus-check", action="store_true",
-                    help="skip the whole-corpus check (every block's storeSize from the timed steps vs the oracle)")
+                    help="--full without the whole-corpus check (every block's storeSize from the timed steps vs "
+                         "the oracle)")
     ap.add_argument("--serial", action="store_true",
                     help="one batch at a time (no stream overlap): clean per-kernel stage times")
     ap.add_argument("--read-blocks", type=int, default=0,
@@ -146,8 +160,7 @@ def parse():
                          "batches overlap while the front halves of the next ones run)")
     ap.add_argument("--alone", action="store_true",
                     help="after the timed region, one untimed serial pass: per-kernel rooflines without co-running "
-                         "batches (on by default for the config-2 line; --no-alone when the bench runs under a "
-                         "profiler whose summary must hold only the timed pipeline's kernels)")
+                         "batches (part of --full for the config-2 line; --no-alone turns it off there)")
     ap.add_argument("--no-alone", action="store_true")
     ap.add_argument("--no-prime", action="store_true",
                     help="drain the pipeline and reset synchronously at every step (the round-4 step shape; "
@@ -182,9 +195,9 @@ def parse():
     ap.add_argument("--mixed", action="store_true",
                     help="config5: config 4's mixed-entropy corpus instead of config 2's")
     ap.add_argument("--no-sub", action="store_true",
-                    help="config 2 at N=1 also runs short config-4 and config-5 lines (the reference's default "
-                         "compressor 2, DN/DataNode.java:438) as child processes before its own run and carries "
-                         "them under \"configs\"; this turns them off")
+                    help="with --full, config 2 at N=1 also runs short config-4 and config-5 lines (the reference's "
+                         "default compressor 2, DN/DataNode.java:438) as child processes before its own run and "
+                         "carries them under \"configs\"; this turns them off")
     ap.add_argument("--workload", choices=["config2", "config4", "config5"], default="config2",
                     help="config4: mixed-entropy blocks (random/text/binary), dedup + Lz4Codec containers; "
                          "config5: host-resident (pinned) blocks streamed H2D on a side stream (PCIe-inclusive)")
@@ -211,8 +224,11 @@ def packet_driver_line(a):
     cmd = [exe, str(nb), str(a.block_mib), str(pk), str(a.packet_threads), str(a.steps), "--compressor",
            str(compressor), "--mirror", a.mirror, "--arena-slots", str(a.arena_slots or 512)]
     cmd += ["--batch"] * a.packet_batch + ["--mixed"] * a.mixed
+    if a.dump_outputs:
+        raise SystemExit("--dump-outputs: the native packet driver's timed steps keep no results; use the in-process "
+                         "config5 line (--packet-driver python)")
     out_dir = None
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         # one more, untimed step keeps its results: every block's storeSize, the sample's chunks and
         # the containers its closes wrote (bench.py checks them against the oracle below)
         out_dir = tempfile.mkdtemp(prefix="hdrf_c5pk_")
@@ -229,8 +245,10 @@ def packet_driver_line(a):
         raise SystemExit("packet driver failed (%d): %s %s" % (r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
     d = json.loads(r.stdout.strip().splitlines()[-1])
     S = a.block_mib << 20
-    import torch                              # (torch initialises HIP before libhdrf does in this process)
-    link = link_probe(torch, 0, S)
+    link = None
+    if a.full:
+        import torch                          # (torch initialises HIP before libhdrf does in this process)
+        link = link_probe(torch, 0, S)
     check = None
     if out_dir:
         try:
@@ -351,8 +369,8 @@ def sub_configs():
     for name, args in SUB_RUNS.items():
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args + ["--no-sub"], capture_output=True,
-                               text=True, timeout=420, env=dict(os.environ))
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args + ["--full", "--no-sub"],
+                               capture_output=True, text=True, timeout=420, env=dict(os.environ))
             lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
             if r.returncode != 0 or not lines:
                 out[name] = {"error": "rc %d: %s" % (r.returncode, (r.stderr or r.stdout)[-600:])}
@@ -364,7 +382,7 @@ def sub_configs():
         d.pop("stages", None)
         if isinstance(d.get("roofline"), dict):
             d["roofline"].pop("alone", None)
-        d["command"] = "python bench.py " + " ".join(args)
+        d["command"] = "python bench.py " + " ".join(args + ["--full"])
         d["wall_s"] = round(time.perf_counter() - t0, 1)
         out[name] = d
         print("sub-line %s: %.3f %s (%.0f s)" % (name, d.get("value") or 0, d.get("unit"), d["wall_s"]),
@@ -373,8 +391,13 @@ def sub_configs():
 
 
 def pcie_entry(value, h2d_bytes, d2h_bytes, step_s, link):
-    """The link figures of a config-5 line: the raw probes and what the step moved over PCIe."""
+    """The link figures of a config-5 line: the raw probes (--full; link None without them) and what
+    the step moved over PCIe."""
     moved = (h2d_bytes + d2h_bytes) / step_s / 1e9
+    if link is None:
+        return {"link_GB_s": round(moved, 2), "drained_container_bytes_per_step": int(d2h_bytes),
+                "d2h_GB_s_drain": round(d2h_bytes / step_s / 1e9, 2),
+                "raw_copy": None, "raw_copy_note": "the raw link probe runs with --full"}
     return {"h2d_GB_s_raw_copy": round(link["h2d"], 2), "d2h_GB_s_raw_copy": round(link["d2h"], 2),
             "bidirectional_GB_s_raw_copy": round(link["bidir"], 2),
             "bidirectional_split_GB_s": {"h2d": round(link["bidir_h2d"], 2), "d2h": round(link["bidir_d2h"], 2)},
@@ -415,7 +438,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     subs = None
-    if world == 1 and a.workload == "config2" and not a.no_sub and not a.serial:
+    if a.full and world == 1 and a.workload == "config2" and not a.no_sub and not a.serial:
         subs = sub_configs()                             # before this process initialises the GPU
     local = int(os.environ.get("LOCAL_RANK", "0"))
     import numpy as np
@@ -477,7 +500,7 @@ def main():
         hbuf = ctx.host_alloc(nb * S)
         ctx.L.hdrf_memcpy_d2h(ctx._h, hbuf.ctypes.data, dev, nb * S)
         dbuf = None if a.no_drain else ctx.host_alloc(1 << 30)   # the drained container files (pinned)
-        link = link_probe(torch, local, S)
+        link = link_probe(torch, local, S) if a.full else None
     batches = []
     for b0 in range(0, nb, B):
         k = min(B, nb - b0)
@@ -688,8 +711,11 @@ def main():
                       "phases": {names[i]: {"share": round(v[i] / max(1, tot), 4),
                                             "cyc_per_event": round(v[i] / max(1, per_ev[i]), 1)}
                                  for i in range(8) if v[i]}}
+    if a.dump_outputs:
+        # before any untimed pass below resets the context: hdrf_batch_* still report the last timed batch
+        dump_outputs(a.dump_outputs, ctx, n_chunks, store, rank, world)
     alone_ms = None
-    alone = (a.alone or (a.workload == "config2" and not a.no_alone)) and not a.no_alone
+    alone = (a.alone or (a.full and a.workload == "config2")) and not a.no_alone
     if alone and node is None and not a.serial and not host:
         # one extra, untimed serial pass (one batch at a time): the same kernels without the
         # co-running batch, for the per-kernel "alone" rooflines next to the in-pipeline ones
@@ -874,7 +900,7 @@ def main():
         read_side = read_bench(ctx, dev, S, min(a.read_blocks, nb), a.hasher, compressor)
     cpu = None
     m_cpu = min(a.cpu_sample_blocks or B, nb)
-    if rank == 0 and world == 1 and not a.no_cpu and m_cpu > 0:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu and m_cpu > 0:
         # the GPU's per-chunk results for the sample (one untimed pass from a fresh index, the same
         # batches as the timed steps), checked chunk by chunk against the all-cores oracle run
         ctx.reset()
@@ -889,7 +915,7 @@ def main():
                     done += 1
         cpu = cpu_baseline(ctx, dev, S, m_cpu, store, a.hasher, compressor, gpu_res)
 
-    if rank == 0 and world == 1 and not a.no_cpu and not a.no_corpus_check:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu and not a.no_corpus_check:
         # the metric's "bit-exact dedup ratio" over the WHOLE corpus: every block's storeSize from the
         # last timed step against the oracle in store-size mode, one batch at a time
         dedup["oracle_check"] = corpus_check(ctx, dev, S, nb, B, store, a.hasher, compressor,
@@ -911,7 +937,9 @@ def main():
                            "batches_in_flight": node.depth if node is not None else a.depth, "steps_back_to_back": bool(primed),
                            "parallelism": "dp%d: blocks sharded by rank; one index partitioned by digest prefix"
                                           % world},
-                "roofline": roofline, "cpu_baseline": cpu, "dedup": dedup, "stages": stages}
+                "roofline": roofline, "cpu_baseline": cpu, "dedup": dedup, "stages": stages, "full": bool(a.full)}
+        if a.dump_outputs:
+            line["outputs_dir"] = a.dump_outputs
         if compression:
             line["compression"] = compression
         if subs:
@@ -944,6 +972,50 @@ def main():
     ctx.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 48 << 20        # bytes of per-chunk arrays --dump-outputs writes (the whole dump stays below 64 MB)
+
+
+def dump_outputs(out_dir, ctx, n_chunks, store, rank, world):
+    """What the last timed step handed its caller, as <name>.npy (rank r of N > 1: <name>_rank<r>.npy):
+    n_chunks / store_size   every block's chunk count and storeSize (hdrf_batch_info, read inside the
+                            timed region), float64 (exact)
+    stats / allocator       hdrf_get_stats (since the step's reset) with the index's entry count, and
+                            the 24-byte allocator state (single-node contexts)
+    last_batch_block<i>_*   the per-chunk results the library holds for the last batch (hdrf_batch_*):
+                            END offsets, container id and position (float64), digest bytes and is_new
+                            (float32), for a fixed sample of its blocks (first, middle, last) and, where a
+                            block alone exceeds the budget, a seeded sample of its chunks (rows in order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+
+    def save(name, arr, dt):
+        np.save(os.path.join(out_dir, name + tag + ".npy"), np.ascontiguousarray(arr, dtype=dt))
+
+    save("n_chunks", n_chunks, np.float64)
+    save("store_size", store, np.float64)
+    if world == 1:
+        st = ctx.stats()
+        save("stats", [st[k] for k in sorted(st)] + [ctx.index_count()], np.float64)
+        save("allocator", np.frombuffer(ctx.allocator() or b"", np.uint8), np.float32)
+    k = ctx.last_nblocks()
+    picks = sorted({0, k // 2, k - 1}) if k > 0 else []
+    row_bytes = 3 * 8 + 4 * (ctx.H + 1)
+    rows_max = DUMP_BUDGET // row_bytes // max(1, len(picks))
+    for i in picks:
+        r = ctx.batch_result(i)
+        n = len(r["offsets"])
+        sel = slice(None)
+        if n > rows_max:
+            sel = np.sort(np.random.default_rng(20251015 + i).choice(n, rows_max, replace=False))
+        pre = "last_batch_block%d_" % i
+        save(pre + "offsets", r["offsets"][sel], np.float64)
+        save(pre + "container_id", r["container_id"][sel], np.float64)
+        save(pre + "container_pos", r["container_pos"][sel], np.float64)
+        save(pre + "digests", r["digests"][sel], np.float32)
+        save(pre + "is_new", r["is_new"][sel], np.float32)
 
 
 PASSES = 5
