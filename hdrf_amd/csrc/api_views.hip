@@ -1,0 +1,494 @@
+// api_views.hip — libhdrf C-ABI: what a DataNode reads back or restores once batches have completed:
+// index views, restore (index, allocator, recipes), recipes and block lengths, container read / load /
+// unload, the durable-container drain, and reconstruction.
+//
+// The views drain the pipeline and write nothing but the grown scratch buffers (d_rd, d_stage).
+// Restore writes the index table, the allocator (d_alloc, h_alloc, have_alloc), containers and
+// recipes; load / unload write ctx->loaded; hdrf_drain_containers writes the drain bookkeeping
+// (pend_closed, undrained, handed) and the drain job list (h_xfer).
+#include "ctx.hpp"
+
+// ---- index views ------------------------------------------------------------------------
+static void encode_value(const IndexEntry &e, uint8_t v[11])
+{
+    // chunkMeta.getMeta — DN/chunkMeta.java:62-77
+    v[0] = (uint8_t)e.ncopy;
+    v[1] = (uint8_t)(e.cid >> 16); v[2] = (uint8_t)(e.cid >> 8); v[3] = (uint8_t)e.cid;
+    v[4] = (uint8_t)(e.start >> 16); v[5] = (uint8_t)(e.start >> 8); v[6] = (uint8_t)e.start;
+    v[7] = (uint8_t)(e.stop >> 16); v[8] = (uint8_t)(e.stop >> 8); v[9] = (uint8_t)e.stop;
+    v[10] = (uint8_t)(((e.start >> 20) & 0xF0) | ((e.stop >> 24) & 0x0F));
+}
+
+static void entry_digest(const IndexEntry &e, int H, uint8_t *out)
+{
+    if (H == 20) {                                   // SHA-1: bytes 0..7 kept in dig[3..4]
+        std::memcpy(out, &e.dig[3], 8);
+    } else {                                         // SHA-224: bytes 0..6 in the tag, 7 in ncopy
+        const unsigned long long t = e.tag & kTag56;
+        std::memcpy(out, &t, 7);
+        out[7] = (uint8_t)(e.ncopy >> 8);
+    }
+    std::memcpy(out + 8, e.dig, H == 20 ? 12 : H - 8);
+}
+
+extern "C" int hdrf_index_get(hdrf_ctx *ctx, const uint8_t *digest, uint8_t out11[11])
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !digest) return HDRF_E_INVAL;
+    uint32_t dw[2];
+    std::memcpy(dw, digest, 8);
+    const unsigned long long key = tag_mask(ctx), tag = tag_word(dw, key);
+    const uint64_t mask = (1ull << ctx->cfg.index_log2) - 1;
+    uint64_t h = tag_home(tag, ctx->cfg.index_log2);
+    if (int rc = drain(ctx)) return rc;
+    for (uint64_t probe = 0; probe <= mask; probe++) {
+        IndexEntry e;
+        HIPCK(hipMemcpy(&e, ctx->d_tab + h, sizeof e, hipMemcpyDeviceToHost));
+        if (!tag_live(e.tag, key)) return 0;
+        uint8_t full[28];
+        entry_digest(e, ctx->H, full);
+        if (e.tag == tag && std::memcmp(full, digest, ctx->H) == 0) {
+            if (out11) encode_value(e, out11);
+            return 1;
+        }
+        h = (h + 1) & mask;
+    }
+    return 0;
+}
+
+static int fetch_table(hdrf_ctx *ctx, std::vector<IndexEntry> &tab)
+{
+    tab.resize((size_t)1 << ctx->cfg.index_log2);
+    if (int rc = drain(ctx)) return rc;
+    HIPCK(hipMemcpy(tab.data(), ctx->d_tab, tab.size() * sizeof(IndexEntry), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Probe lengths of the last completed batch (linear probing from each chunk's home slot to the
+// entry it resolved to): sum, max and the number of chunks.  Steady-state index measurement.
+extern "C" int hdrf_probe_stats(hdrf_ctx *ctx, int64_t *probe_sum, int64_t *probe_max, int64_t *chunks)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !probe_sum || !probe_max || !chunks) return HDRF_E_INVAL;
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "probe stats on node-global contexts");
+    if (int rc = drain(ctx)) return rc;
+    Slot &S = ctx->sl[ctx->res];
+    if (ctx->last_nblocks < 1) return set_err(ctx, HDRF_E_INVAL, "no completed batch");
+    unsigned long long *d = nullptr;
+    HIPCK(hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
+    unsigned long long h[3] = {0, 0, 0};
+    hipError_t e = hipMemsetAsync(d, 0, sizeof h, ctx->st);
+    if (e == hipSuccess)
+        e = launch_index_probe(ctx->cfg.hasher, S.d_bst, ctx->last_nblocks, ctx->cap_blk, S.d_dig, S.d_slot,
+                               ctx->cfg.index_log2, tag_mask(ctx), d, ctx->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_err(ctx, HDRF_E_HIP, hipGetErrorString(e));
+    *probe_sum = (int64_t)h[0];
+    *probe_max = (int64_t)h[1];
+    *chunks = (int64_t)h[2];
+    return 0;
+}
+
+extern "C" int64_t hdrf_index_count(hdrf_ctx *ctx)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    std::vector<IndexEntry> tab;
+    if (int rc = fetch_table(ctx, tab)) return rc;
+    int64_t n = 0;
+    const unsigned long long key = tag_mask(ctx);
+    for (auto &e : tab) n += tag_live(e.tag, key);
+    return n;
+}
+
+extern "C" int64_t hdrf_index_dump(hdrf_ctx *ctx, uint8_t *keys, uint8_t *vals, int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    std::vector<IndexEntry> tab;
+    if (int rc = fetch_table(ctx, tab)) return rc;
+    const int H = ctx->H;
+    std::vector<std::vector<uint8_t>> rows;
+    const unsigned long long key = tag_mask(ctx);
+    for (auto &e : tab) {
+        if (!tag_live(e.tag, key)) continue;
+        std::vector<uint8_t> r(H + 11);
+        entry_digest(e, H, r.data());
+        encode_value(e, r.data() + H);
+        rows.push_back(std::move(r));
+    }
+    if ((int64_t)rows.size() > cap) return set_err(ctx, HDRF_E_CAPACITY, "index dump capacity");
+    std::sort(rows.begin(), rows.end(),
+              [H](const std::vector<uint8_t> &a, const std::vector<uint8_t> &b) { return std::memcmp(a.data(), b.data(), H) < 0; });
+    for (size_t i = 0; i < rows.size(); i++) {
+        std::memcpy(keys + i * H, rows[i].data(), H);
+        std::memcpy(vals + i * 11, rows[i].data() + H, 11);
+    }
+    return (int64_t)rows.size();
+}
+
+extern "C" int hdrf_allocator(hdrf_ctx *ctx, uint8_t out24[24])
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !out24) return HDRF_E_INVAL;
+    if (!ctx->have_alloc) return 0;
+    uint32_t v[8];
+    for (int t = 0; t < 4; t++) {
+        v[t] = ctx->h_alloc.id[t];
+        v[t + 4] = ctx->h_alloc.pos[t];
+    }
+    for (int i = 0; i < 8; i++) {                   // utilities.blockIDtoBytes (DN/utilities.java:66-75)
+        out24[3 * i] = (uint8_t)(v[i] >> 16);
+        out24[3 * i + 1] = (uint8_t)(v[i] >> 8);
+        out24[3 * i + 2] = (uint8_t)v[i];
+    }
+    return 1;
+}
+
+// ---- restore (index persistence: a DataNode restarting on its Redis dump + chunkDir) -------
+// SET digest -> value for n entries (the rows of hdrf_index_dump) on a context whose index does
+// not hold these digests yet (a fresh or reset context).
+extern "C" int hdrf_index_load(hdrf_ctx *ctx, const uint8_t *keys, const uint8_t *vals, int64_t n)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || n < 0 || (n && (!keys || !vals))) return HDRF_E_INVAL;
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "restore on node-global contexts: not yet");
+    if (int rc = drain(ctx)) return rc;
+    if (n == 0) return 0;
+    const uint64_t o_dw = 0, dw_b = (uint64_t)n * ctx->HW * 4;
+    const uint64_t o_v = (dw_b + 255) & ~255ull, o_err = (o_v + (uint64_t)n * 11 + 255) & ~255ull;
+    if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, o_err + 256)) return rc;
+    uint8_t *R = ctx->d_rd;
+    hipStream_t st = ctx->st;
+    std::vector<uint8_t> dw(dw_b, 0);                  // digest bytes as u32 words (SHA-224: 28 B)
+    for (int64_t k = 0; k < n; k++) std::memcpy(dw.data() + (size_t)k * ctx->HW * 4, keys + (size_t)k * ctx->H, ctx->H);
+    HIPCK(hipMemcpyAsync(R + o_dw, dw.data(), dw_b, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(R + o_v, vals, (size_t)n * 11, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(R + o_err, 0, 4, st));
+    HIPCK(launch_index_load(ctx->cfg.hasher, (const uint32_t *)(R + o_dw), R + o_v, (int)n, ctx->d_tab,
+                            ctx->cfg.index_log2, tag_mask(ctx), ++ctx->batch, (int *)(R + o_err), st));
+    int err = 0;
+    HIPCK(hipMemcpyAsync(&err, R + o_err, 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (err) return set_err(ctx, HDRF_E_CAPACITY, "index table full (index_log2 too small)");
+    return 0;
+}
+
+// SET "blockID" (the 24-B allocator, DN/utilities.java:66-75) and reopen the three storer
+// ranges' open containers from their chunkDir files (open_len[t] < 0: no file): the storer
+// appends to them exactly as threadedStorer does after reading prevData (:723-737).
+extern "C" int hdrf_allocator_load(hdrf_ctx *ctx, const uint8_t alloc24[24], const uint8_t *const *open_files,
+                                   const int64_t *open_len)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !alloc24 || !open_len) return HDRF_E_INVAL;
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "restore on node-global contexts: not yet");
+    if (int rc = drain(ctx)) return rc;
+    AllocState a{};
+    for (int i = 0; i < 8; i++) {
+        const uint32_t v = ((uint32_t)alloc24[3 * i] << 16) | ((uint32_t)alloc24[3 * i + 1] << 8) | alloc24[3 * i + 2];
+        if (i < 4) a.id[i] = v; else a.pos[i - 4] = v;
+    }
+    for (int t = 0; t < 4; t++) a.slot[t] = (uint32_t)t * (uint32_t)(ctx->cfg.arena_slots / 4);
+    for (int t = 0; t < ctx->cfg.n_thread; t++) {
+        if (open_len[t] < 0) continue;
+        if ((uint64_t)open_len[t] > ctx->cfg.container_max || (open_len[t] && (!open_files || !open_files[t])))
+            return set_err(ctx, HDRF_E_INVAL, "bad open container file");
+        if (open_len[t])
+            HIPCK(hipMemcpy(ctx->d_arena + (size_t)a.slot[t] * ctx->cfg.container_max, open_files[t],
+                            (size_t)open_len[t], hipMemcpyHostToDevice));
+        a.cur[t] = (uint32_t)open_len[t];
+        a.exists[t] = 1;
+    }
+    HIPCK(hipMemcpy(ctx->d_alloc, &a, sizeof a, hipMemcpyHostToDevice));
+    ctx->h_alloc = a;
+    ctx->have_alloc = 1;
+    for (int t = 0; t < ctx->cfg.n_thread; t++)
+        if (a.exists[t]) note_container(ctx, a.id[t], a.slot[t], a.cur[t], 0);
+    return 0;
+}
+
+// SET longToBytes(blockId,4) -> recipe (storeDB, DN/DataDeduplicator.java:372-392)
+extern "C" int hdrf_recipe_load(hdrf_ctx *ctx, uint64_t block_id, const uint8_t *recipe, int64_t len)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !recipe || len < 4 || (len - 4) % ctx->H) return HDRF_E_INVAL;
+    const uint32_t key = (uint32_t)block_id;
+    if (int rc = drain(ctx)) return rc;
+    const uint32_t n = (uint32_t)((len - 4) / ctx->H);
+    uint8_t *dst = nullptr;
+    if (int rc = recipe_alloc(ctx, (uint64_t)n * ctx->H, key, n, &dst)) return rc;
+    if (n) HIPCK(hipMemcpy(dst, recipe + 4, (size_t)n * ctx->H, hipMemcpyHostToDevice));
+    ctx->lengths[key] = ((int64_t)recipe[0] << 24) | (recipe[1] << 16) | (recipe[2] << 8) | recipe[3];
+    return 0;
+}
+
+extern "C" int64_t hdrf_recipe_get(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (int rc = drain(ctx)) return rc;                 // blocks in flight first: their recipes are SET
+    auto it = ctx->recipes.find((uint32_t)block_id);
+    if (it == ctx->recipes.end()) return 0;
+    const int64_t n = 4 + (int64_t)it->second.n * ctx->H;
+    if (!out || cap < n) return set_err(ctx, HDRF_E_CAPACITY, "recipe needs " + std::to_string(n) + " bytes");
+    std::vector<uint8_t> r;
+    const int fr = fetch_recipe(ctx, (uint32_t)block_id, r);
+    if (fr < 0) return fr;
+    std::memcpy(out, r.data(), (size_t)n);
+    return n;
+}
+
+extern "C" int64_t hdrf_block_length(hdrf_ctx *ctx, uint64_t block_id)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    auto it = ctx->lengths.find((uint32_t)block_id);
+    return it == ctx->lengths.end() ? HDRF_E_NOTFOUND : it->second;
+}
+
+extern "C" int64_t hdrf_container_read(hdrf_ctx *ctx, uint32_t id, uint8_t *out, int64_t cap, int32_t *closed)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (int rc = drain(ctx)) return rc;                 // batches in flight may append, close or recycle it
+    auto it = ctx->containers.find(id);
+    if (it == ctx->containers.end()) return set_err(ctx, HDRF_E_NOTFOUND, "container not resident");
+    if (closed) *closed = it->second.closed;
+    const bool lz = ctx->cfg.compressor == 2 && it->second.closed;     // the file is the Lz4Codec stream
+    const int64_t n = lz ? it->second.clen : it->second.len;
+    if (!out) return n;
+    if (cap < n) return set_err(ctx, HDRF_E_CAPACITY, "container capacity");
+    const uint8_t *src = lz ? ctx->d_carena + (size_t)it->second.slot * ctx->cslot
+                            : ctx->d_arena + (size_t)it->second.slot * ctx->cfg.container_max;
+    if (n) HIPCK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+    return n;
+}
+
+// Make container `id` readable for reconstruction from its chunkDir file (raw, or a closed
+// container's Lz4Codec file): a DataNode that restarted, or whose arena slot was reused.
+extern "C" int hdrf_container_load(hdrf_ctx *ctx, uint32_t id, const uint8_t *file, int64_t flen, int32_t lz4)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || flen < 0 || (flen && !file)) return HDRF_E_INVAL;
+    uint64_t raw = (uint64_t)flen;
+    if (lz4) {
+        std::vector<LzDec> items;
+        if (!plan_lz4_frame(file, flen, items, &raw)) return set_err(ctx, HDRF_E_INVAL, "malformed Lz4Codec frame");
+    }
+    if (raw > ctx->cfg.container_max) return set_err(ctx, HDRF_E_INVAL, "container larger than container_max");
+    if (int rc = drain(ctx)) return rc;
+    uint8_t *p = nullptr;
+    HIPCK(hipMalloc((void **)&p, raw + 64));
+    int64_t got = (int64_t)raw;
+    if (lz4) got = decode_file(ctx, file, flen, p, (int64_t)raw);
+    else if (raw) {
+        if (hipMemcpy(p, file, raw, hipMemcpyHostToDevice) != hipSuccess) got = set_err(ctx, HDRF_E_HIP, "H2D copy");
+    }
+    if (got < 0) { (void)hipFree(p); return (int)got; }
+    auto it = ctx->loaded.find(id);
+    if (it != ctx->loaded.end()) (void)hipFree(it->second.ptr);
+    ctx->loaded[id] = hdrf_ctx::Loaded{p, raw};
+    return 0;
+}
+
+extern "C" int hdrf_container_unload(hdrf_ctx *ctx, uint32_t id)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (int rc = drain(ctx)) return rc;
+    auto it = ctx->loaded.find(id);
+    if (it == ctx->loaded.end()) return set_err(ctx, HDRF_E_NOTFOUND, "container not loaded");
+    (void)hipFree(it->second.ptr);
+    ctx->loaded.erase(it);
+    return 0;
+}
+
+// ---- durable containers: the chunkDir files of the storers (DN/DataDeduplicator.java:748-818) ----
+// Since the last drain: every container that closed (the whole file: raw bytes, or the Lz4Codec
+// stream under compressor 2, rewritten at :748-786) in close order, then every open container's
+// bytes appended since (:806-818).  Events are emitted whole, in order, while they fit.  Only what
+// the COMPLETED batches (hdrf_wait_batch) produced is handed out; batches still in flight keep
+// running: their place kernels only append past the bytes copied here, and a closed container's
+// slot stays retained until it is drained.  The D2H copies run on stream D, so they overlap the
+// H2D copies of later batches on stream C (PCIe is full duplex).
+extern "C" int64_t hdrf_drain_containers(hdrf_ctx *ctx, hdrf_container_event *ev, int64_t ev_cap, uint8_t *out,
+                                         int64_t out_cap, int64_t *need)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (need) *need = 0;
+    if (!ctx->cfg.retain_containers) return set_err(ctx, HDRF_E_INVAL, "hdrf_drain_containers needs cfg.retain_containers");
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "container drain on node-global contexts");
+    if (ev_cap < 0 || out_cap < 0 || (ev_cap && !ev) || (out_cap && !out)) return set_err(ctx, HDRF_E_INVAL, "bad buffers");
+    const hdrf_cfg &c = ctx->cfg;
+    struct Pend { uint32_t id; int closed; int64_t off, n; ContainerInfo ci; };
+    std::vector<Pend> todo;
+    for (uint32_t id : ctx->pend_closed) {
+        auto it = ctx->containers.find(id);
+        if (it == ctx->containers.end()) return set_err(ctx, HDRF_E_DEVICE, "undrained container missing");
+        if (c.compressor == 2) {                          // the whole Lz4Codec file replaces the raw one
+            todo.push_back(Pend{id, 1, 0, (int64_t)it->second.clen, it->second});
+        } else {
+            // the storer's close rewrites the file as prevData || buffer (:754-786): the bytes already
+            // handed out plus the rest, so only the rest travels (file_off = the bytes handed out)
+            const int64_t done = ctx->handed.count(id) ? ctx->handed[id] : 0;
+            todo.push_back(Pend{id, 1, done, (int64_t)it->second.len - done, it->second});
+        }
+    }
+    const size_t nclosed = todo.size();
+    for (int t = 0; t < c.n_thread; t++) {
+        if (!ctx->h_alloc.exists[t]) continue;
+        const uint32_t id = ctx->h_alloc.id[t];
+        auto it = ctx->containers.find(id);
+        if (it == ctx->containers.end()) continue;
+        const int64_t done = ctx->handed.count(id) ? ctx->handed[id] : 0;
+        if ((int64_t)it->second.len > done) todo.push_back(Pend{id, 0, done, (int64_t)it->second.len - done, it->second});
+    }
+    // pinned (device-mapped) output: the CUs write it (xfer_kernel), beside the SDMA H2D of later
+    // batches (whole blocks through hdrf_submit_host: 38.8 / 39.1 vs 34.7 / 35.5 GB/s with the copy
+    // engine); once the context receives packets (hdrf_rx_begin), the copy engine (22.0 vs 28.3 GB/s
+    // for 64 KiB packets, profiles/r03_c5_drain_ab.txt); pageable output: hipMemcpyAsync.
+    // HDRF_DRAIN_KERNEL=1 / 0 forces the CUs / the copy engine.
+    static const int kern_env = [] { const char *e = getenv("HDRF_DRAIN_KERNEL"); return e ? (atoi(e) != 0) : -1; }();
+    const bool kern = kern_env >= 0 ? kern_env != 0 : !ctx->rx_used;
+    hipPointerAttribute_t pa;
+    const bool mapped = kern && out_cap > 0 && hipPointerGetAttributes(&pa, out) == hipSuccess &&
+                        pa.type == hipMemoryTypeHost && pa.devicePointer != nullptr;
+    (void)hipGetLastError();
+    if (mapped && ctx->xfer_cap == 0) {
+        HIPCK(hipHostMalloc((void **)&ctx->h_xfer, sizeof(XferJob) * 1024, hipHostMallocDefault));
+        ctx->xfer_cap = 1024;
+    }
+    int64_t k = 0, used = 0;
+    int nj = 0;
+    uint64_t maxj = 0;
+    // CU drain grid: one workgroup per ~256 MiB of this drain, at least 5.  Five workgroups still drain
+    // a config-5 batch in ~19.5 ms, but the next blocks' H2D copies beside them keep 54.9 GB/s, where
+    // a full grid's flood of PCIe writes cut them to 44.6 (config 5 whole blocks: 50.0 / 50.1 GB/s
+    // with 5 workgroups, 49.8 / 48.5 with 4, 41.5 with 3, 47.3 / 47.4 with one per item;
+    // profiles/r04_drain_wgs_ab.txt, r04_c5_trace3.txt).  HDRF_XFER_WGS = W overrides (0: one per item).
+    static const int wgs_env = env_int("HDRF_XFER_WGS", -1);
+    int64_t drain_bytes = 0;
+    for (const Pend &e : todo) drain_bytes += e.n;
+    const int wgs = wgs_env >= 0 ? wgs_env : (int)std::max<int64_t>(5, (drain_bytes + (256ll << 20) - 1) / (256ll << 20));
+    for (const Pend &e : todo) {
+        if (k >= ev_cap || used + e.n > out_cap) {
+            if (need) *need = e.n;
+            break;
+        }
+        const uint8_t *src = (e.closed && c.compressor == 2) ? ctx->d_carena + (size_t)e.ci.slot * ctx->cslot
+                                                             : ctx->d_arena + (size_t)e.ci.slot * c.container_max;
+        if (e.n && mapped) {
+            if (nj == ctx->xfer_cap) {                    // job list full: flush it
+                HIPCK(launch_xfer(ctx->h_xfer, nj, maxj, wgs, ctx->stD));
+                HIPCK(hipStreamSynchronize(ctx->stD));
+                nj = 0;
+                maxj = 0;
+            }
+            ctx->h_xfer[nj++] = XferJob{(uint64_t)(uintptr_t)(src + e.off),
+                                        (uint64_t)(uintptr_t)((uint8_t *)pa.devicePointer + used), (uint64_t)e.n};
+            maxj = std::max<uint64_t>(maxj, (uint64_t)e.n);
+        } else if (e.n) {
+            HIPCK(hipMemcpyAsync(out + used, src + e.off, (size_t)e.n, hipMemcpyDeviceToHost, ctx->stD));
+        }
+        ev[k] = hdrf_container_event{e.id, e.closed, e.off, e.n, used};
+        used += e.n;
+        k++;
+    }
+    if (nj) HIPCK(launch_xfer(ctx->h_xfer, nj, maxj, wgs, ctx->stD));
+    HIPCK(hipStreamSynchronize(ctx->stD));
+    // the emitted ones are handed over
+    const size_t kc = std::min<size_t>((size_t)k, nclosed);
+    for (size_t i = 0; i < kc; i++) {
+        const uint32_t id = ctx->pend_closed[i];
+        ctx->undrained[std::min<uint32_t>(id >> 22, 3)]--;
+        ctx->handed.erase(id);
+    }
+    ctx->pend_closed.erase(ctx->pend_closed.begin(), ctx->pend_closed.begin() + kc);
+    for (size_t i = nclosed; i < (size_t)k; i++) ctx->handed[todo[i].id] = todo[i].off + todo[i].n;
+    if (k == 0 && !todo.empty()) return set_err(ctx, HDRF_E_CAPACITY, "drain buffer too small for the next event");
+    return k;
+}
+
+// ---- read side: DataConstructor (DN/DataConstructor.java:73-250, 360-531) --------------------
+int host::grow(hdrf_ctx *ctx, uint8_t **p, uint64_t *cap, uint64_t need)
+{
+    if (*cap >= need) return 0;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIPCK(hipMalloc((void **)p, need));
+    *cap = need;
+    return 0;
+}
+
+extern "C" int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out,
+                                    int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !recipe || recipe_len < 4) return HDRF_E_INVAL;
+    if (ctx->G > 1)
+        return set_err(ctx, HDRF_E_UNSUPPORTED, "node-global contexts read through hdrf_gx_read_locate / _fill (every rank)");
+    if (int rc = drain(ctx)) return rc;
+    const int64_t size = ((int64_t)recipe[0] << 24) | (recipe[1] << 16) | (recipe[2] << 8) | recipe[3];
+    const int64_t n = recipe_len / ctx->H;             // t1data.length / hash_length (:223)
+    if (size > cap || (size && !dev_out)) return set_err(ctx, HDRF_E_CAPACITY, "output capacity");
+    if (n == 0) return size == 0 ? 0 : set_err(ctx, HDRF_E_DEVICE, "recipe without digests");
+    // readable containers sorted by id: arena-resident ones, then those loaded back from files
+    std::map<uint32_t, uint64_t> rdbl;
+    for (auto &kv : ctx->loaded) rdbl[kv.first] = (uint64_t)(uintptr_t)kv.second.ptr;
+    for (auto &kv : ctx->containers)
+        rdbl[kv.first] = (uint64_t)(uintptr_t)(ctx->d_arena + (size_t)kv.second.slot * ctx->cfg.container_max);
+    std::vector<uint32_t> cid;
+    std::vector<uint64_t> base;
+    for (auto &kv : rdbl) { cid.push_back(kv.first); base.push_back(kv.second); }
+    const int ncont = (int)cid.size();
+    const uint64_t o_dig = 0, dig_b = (uint64_t)n * ctx->HW * 4;
+    const uint64_t o_ch = (dig_b + 255) & ~255ull, ch_b = (uint64_t)n * rd_chunk_bytes();
+    const uint64_t o_base = (o_ch + ch_b + 255) & ~255ull, base_b = (uint64_t)std::max(1, ncont) * 8;
+    const uint64_t o_cid = (o_base + base_b + 255) & ~255ull, cid_b = (uint64_t)std::max(1, ncont) * 4;
+    const uint64_t o_tot = (o_cid + cid_b + 255) & ~255ull;
+    if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, o_tot + 256)) return rc;
+    uint8_t *R = ctx->d_rd;
+    hipStream_t st = ctx->st;
+    HIPCK(hipMemcpyAsync(R + o_dig, recipe + 4, (size_t)n * ctx->H, hipMemcpyHostToDevice, st));
+    if (ncont) {
+        HIPCK(hipMemcpyAsync(R + o_cid, cid.data(), cid.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(R + o_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st));
+    }
+    HIPCK(hipMemsetAsync(R + o_tot, 0, 16, st));
+    const uint64_t *bases = (const uint64_t *)(R + o_base);
+    HIPCK(launch_reconstruct(ctx->cfg.hasher, (const uint32_t *)(R + o_dig), (int)n, ctx->d_tab, ctx->cfg.index_log2,
+                             tag_mask(ctx), (const uint32_t *)(R + o_cid), bases, ncont, R + o_ch,
+                             (uint64_t *)(R + o_tot), dev_out, (int *)(R + o_tot + 8), st, false));
+    uint64_t tot[2] = {0, 0};
+    HIPCK(hipMemcpyAsync(tot, R + o_tot, 16, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if ((int)tot[1]) return set_err(ctx, HDRF_E_NOTFOUND, "a recipe digest or its container is not readable");
+    if ((int64_t)tot[0] != size) return set_err(ctx, HDRF_E_DEVICE, "chunk lengths do not add up to the recipe size");
+    HIPCK(launch_reconstruct(ctx->cfg.hasher, nullptr, (int)n, nullptr, 0, 0, nullptr, bases, 0, R + o_ch, nullptr,
+                             dev_out, nullptr, st, true));
+    HIPCK(hipStreamSynchronize(st));
+    return size;
+}
+
+extern "C" int64_t hdrf_reconstruct_block(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (int rc = drain(ctx)) return rc;
+    std::vector<uint8_t> rec;                            // GET longToBytes(blockId,4) (DN/BlockSender.java:292-328)
+    const int fr = fetch_recipe(ctx, (uint32_t)block_id, rec);
+    if (fr < 0) return fr;
+    if (!fr) return set_err(ctx, HDRF_E_NOTFOUND, "no recipe for this block (keep_recipes?)");
+    const int64_t size = ((int64_t)rec[0] << 24) | (rec[1] << 16) | (rec[2] << 8) | rec[3];
+    if (!out || cap < size) return set_err(ctx, HDRF_E_CAPACITY, "needs " + std::to_string(size) + " bytes");
+    if (int rc = grow(ctx, &ctx->d_stage, &ctx->stage_cap, (uint64_t)size + 4096)) return rc;
+    const int64_t got = hdrf_reconstruct(ctx, rec.data(), (int64_t)rec.size(), ctx->d_stage, size);
+    if (got < 0) return got;
+    if (got) HIPCK(hipMemcpy(out, ctx->d_stage, got, hipMemcpyDeviceToHost));
+    return got;
+}

@@ -680,9 +680,6 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 #ifndef HDRF_COOP
 #define HDRF_COOP 1                      // wave-cooperative list and offsets copies (0: per-lane rows, the A/B
 #endif                                   // baseline; profiles/r06_coop*_ab.txt)
-#ifndef HDRF_COOP_META
-#define HDRF_COOP_META 0                 // (build flag, A/B) the walk's SegMeta records stored together
-#endif
 #ifndef HDRF_WALK_LINE
 #define HDRF_WALK_LINE 1                 // (0: half-line units, the A/B baseline; profiles/r06_walkline*_ab.txt)
 #endif
@@ -959,37 +956,18 @@ __global__ void __launch_bounds__(256) lane_walk_kernel(const BlockDesc *__restr
         for (int i = 0; i < n; i++) list[i] = (uint32_t)s + (uint32_t)vcuts[l * kLdsCuts + i];
 #endif
         if (n_main < 0) n_main = n;
-#if !HDRF_COOP_META
+        // (SegMeta records staged through LDS and stored together: +1.5 % run second, -2.3 % run first,
+        // profiles/r06_meta_ab.txt; not adopted)
         SegMeta m;
         m.n_main = n_main; m.n_over = n - n_main; m.sync = sync; m.jmp = 0; m.jj = 0; m.n_ext = 0; m.ext_dst = -1;
         m.cp_from = 0; m.cp_n = 0; m.cp_dst = 0; m.pad[0] = m.pad[1] = m.pad[2] = 0;
         meta[G] = m;
-#endif
         if (k < nseg - 1 && sync < 0) atomicOr(irr + (G >> 5), 1u << (G & 31));   // irregular boundary
         if (sync == kSyncFail) {
             const int q = atomicAdd(rq_count, 1);
             if (q < rq_cap) rq[q] = G;                        // beyond rq_cap: no repair, stitch falls back
         }
     }
-#if HDRF_COOP_META
-    {
-        // the wave's SegMeta records (consecutive, 13 words each) through its LDS list rows, which the
-        // list copy above has read: each lane stages its record, the lanes store the words in order
-        static_assert(sizeof(SegMeta) == 52 && 63 * 52 <= 64 * kLdsCuts * 2, "SegMeta staging");
-        const int nreal = min(kWaveSegs, nseg - wl * kWaveSegs);
-        __attribute__((address_space(3))) volatile uint32_t *st32 =
-            (__attribute__((address_space(3))) volatile uint32_t *)vcuts;
-        if (real) {
-            const int nm = n_main < 0 ? n : n_main;
-            const uint32_t w[13] = {(uint32_t)nm, (uint32_t)(n - nm), (uint32_t)sync, 0u, 0u, 0u, 0xffffffffu,
-                                    0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int i = 0; i < 13; i++) st32[l * 13 + i] = w[i];
-        }
-        uint32_t *mrow = (uint32_t *)(meta + bd.seg0 + wl * kWaveSegs);
-        for (int t = l; t < nreal * 13; t += 64) mrow[t] = st32[t];
-    }
-#endif
 }
 
 // 2. repair: one wave per failed boundary k (queued by the lane walk), the exact sequential walker
@@ -1466,13 +1444,13 @@ __global__ void __launch_bounds__(64) spec_fallback_kernel(const BlockDesc *__re
 
 }  // namespace hdrf
 
-// ---- host-side launchers (called from api.hip) -------------------------------------------
+// ---- host-side launchers (called from api*.hip) ------------------------------------------
 namespace hdrf {
 int lane_spec_cap(int seg_len, int w) { return seg_len / (w + 2) + 2 + kLaneOver; }
 
 int setprio_mask()
 {
-    static const int m = [] { const char *e = getenv("HDRF_SETPRIO"); return e ? atoi(e) : 0; }();
+    static const int m = env_int("HDRF_SETPRIO", 0);
     return m;
 }
 
@@ -1501,7 +1479,7 @@ static hipError_t launch_fused_front(const BlockDesc *d_blocks, int nblocks, int
     // HDRF_FUSED_GM=1: the granule maxima of the blocks with a repaired boundary (the repair walk's
     // long searches skip by them); default none: a boundary of every 4 GiB batch's blocks goes to the
     // repair walk, so the pass ran over the whole batch (4.56 GB, profiles/r06_fz_traffic.json)
-    static const bool fz_gm = [] { const char *v = getenv("HDRF_FUSED_GM"); return v && atoi(v) != 0; }();
+    static const bool fz_gm = env_int("HDRF_FUSED_GM", 0) != 0;
     const uint8_t *gm = fz_gm ? X.gm : nullptr;
     if (fz_gm) {
         const int gx = (int)(((max_len + 15) / 16 + kGmPerWg - 1) / kGmPerWg);
@@ -1550,7 +1528,7 @@ hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_l
     const int prio = setprio_mask();
     const int gx = (int)(((max_len + 15) / 16 + kGmPerWg - 1) / kGmPerWg);
     // HDRF_GMAX_V: 2 (default) gmax2 (15 VALU per granule, one 16-B store per thread), 1 the round-2 pass
-    static const int gver = [] { const char *e = getenv("HDRF_GMAX_V"); return e ? atoi(e) : 2; }();
+    static const int gver = env_int("HDRF_GMAX_V", 2);
     if (gver == 2 && (stream_knobs() & 1))
         hipLaunchKernelGGL(gmax2_kernel<true>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
     else if (gver == 2)
@@ -1566,9 +1544,9 @@ hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_l
     }
     // HDRF_WALK_LDS: dynamic LDS per walk workgroup (occupancy throttle: fewer lanes in flight keep
     // their granule-maximum lines in L2 between chunk steps)
-    static const int walk_lds = [] { const char *v = getenv("HDRF_WALK_LDS"); return v ? atoi(v) : 0; }();
+    static const int walk_lds = env_int("HDRF_WALK_LDS", 0);
     // HDRF_WALK_RING: 1 / 0 force the ring on / off; default: X.ring (the caller's choice)
-    static const int ring_env = [] { const char *v = getenv("HDRF_WALK_RING"); return v ? atoi(v) : -1; }();
+    static const int ring_env = env_int("HDRF_WALK_RING", -1);
     const int ring_on = ring_env >= 0 ? ring_env : X.ring;
     if (ring_on)
         hipLaunchKernelGGL(lane_walk_kernel<true>, dim3((total_waves + 3) / 4), dim3(256), walk_lds, st, d_blocks, nblocks, total_waves,

@@ -167,7 +167,7 @@ struct RangeState {          // per (block, range t)
     int32_t active;              // storer t runs (storeSize != 0 and t < nThread)
 };
 
-// Node-global allocator scan (gx.hip / api.hip hdrf_gx_flush_fn): one range's flush walk over
+// Node-global allocator scan (gx.hip / api_gx.hip hdrf_gx_flush_fn): one range's flush walk over
 // a batch as a function of the open container's fill, with the batch's active blocks of range t
 // laid end to end as one stream of new bytes.
 struct FnBlock {             // per (range t, block b)

@@ -1,14 +1,25 @@
-// launchers.hpp — host-side kernel launchers shared by api.hip (one stream per context).
+// launchers.hpp — host-side kernel launchers shared by the api*.hip files (one stream per context).
 #pragma once
+#include <cstdlib>
+
 #include "common.hpp"
 
 namespace hdrf {
+
+// An integer environment knob (atoi of the variable, dflt when unset).  Not cached: a call site
+// that wants one read per process keeps the value in a static const.  (Hidden: not one of the
+// library's dynamic symbols.)
+__attribute__((visibility("hidden"))) inline int env_int(const char *name, int dflt)
+{
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
 
 // Stage markers: when timing is on, a HIP event is recorded on the launch stream at every
 // stage boundary (kernels of one stream run in order, so event deltas are kernel times).
 // walk, stitch, sha, (unused), claim, apply, slow+decide, scan, flush, place, compress, gmax, then the
 // node-global phases: local aggregation, owner, decide, flush function, allocator scan, placement,
-// commit, and the X1 / X2 / descriptor all-gather / X3 exchanges (api.hip gx_collect)
+// commit, and the X1 / X2 / descriptor all-gather / X3 exchanges (api_gx.hip gx_collect)
 constexpr int kNumStages = 23;
 struct Marker {
     hipEvent_t *ev = nullptr;   // kNumStages + 1 events
@@ -34,7 +45,7 @@ struct StoreParams {
 // chunking: granule maxima -> lane walk (total_waves waves over the batch's segments) -> repair ->
 // stitch -> fallback.  gm: [nblocks][gstride] bytes, gstride >= max_len / 16 + 4 * 128.
 int lane_spec_cap(int seg_len, int w);
-// scratch of one batch's chunking (api.hip slot buffers)
+// scratch of one batch's chunking (ctx.hpp slot buffers)
 struct ChunkScratch {
     uint8_t *gm;             // granule maxima [nblocks][gstride]
     int gstride;

@@ -31,11 +31,8 @@ constexpr int kMfLimit = 12, kLastLit = 5, kMaxDist = 65535, k64KLimit = 65536 +
 constexpr int kLzFirstBatch = 8;                 // attempts per batch after a match (then 16, 32, 64)
 // Bytes of one lane window (forward, reference, search, candidate): 4 per lane over kLzWin / 4
 // lanes; with 128 the upper 32 lanes load the lower 32 lanes' words again (no extra line
-// requests) and take no part in the compares.  HDRF_LZ4_WIN (A/B builds): 256 or 128.
-#ifndef HDRF_LZ4_WIN
-#define HDRF_LZ4_WIN 256
-#endif
-constexpr int kLzWin = HDRF_LZ4_WIN;
+// requests) and take no part in the compares (128 measured inside the spread: profiles/r06_lz4win_ab.txt).
+constexpr int kLzWin = 256;
 constexpr int kLzWinLanes = kLzWin / 4;
 static_assert(kLzWin == 256 || kLzWin == 128, "LZ4 window: 256 or 128 bytes");
 
@@ -757,7 +754,7 @@ hipError_t launch_lz4(const ClosedRec *closed, const uint32_t *nclosed, int clos
             n = 256;
         return n > 0 ? n : 256;
     }();
-    static const int wpc = [] { const char *e = getenv("HDRF_LZ4_WAVES"); const int v = e ? atoi(e) : 16; return v > 0 ? v : 16; }();
+    static const int wpc = [] { const int v = env_int("HDRF_LZ4_WAVES", 16); return v > 0 ? v : 16; }();
     const int nseg_max = (int)((cmax + kLzMaxIn - 1) / kLzMaxIn);
     if (hipError_t e = hipMemsetAsync(work, 0, 2 * sizeof(uint32_t), st)) return e;
     const int prio = (setprio_mask() >> 6) & 1;

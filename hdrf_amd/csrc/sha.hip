@@ -26,27 +26,21 @@ namespace hdrf {
 
 
 // sha_carry: the 65 dwords (260 B) of four blocks at pos (4-aligned down); the second pair's half
-// is carried in registers to the lane's next iteration.  HDRF_SHA_CLAMP (build flag): the 16-B loads
-// past the chunk's last byte (end = its END offset) re-read the last one that holds chunk bytes, so a
-// chain's final window requests no line beyond the chunk (the padding never reads those bytes:
-// pad_block zeroes every word after the message end).
-#ifndef HDRF_SHA_CLAMP
-#define HDRF_SHA_CLAMP 0
-#endif
+// is carried in registers to the lane's next iteration.  (Clamping the 16-B loads at the chunk's last
+// byte, end, cut the fetched lines but cost config 2 about 1 %: profiles/r06_shaclamp_ab.txt.)
 __device__ __forceinline__ void load_win65(const uint8_t *base, uint64_t readable, uint32_t pos, uint32_t end,
                                            uint32_t d[65])
 {
     const uint32_t apos = pos & ~3u;
     if ((uint64_t)apos + 260u <= readable) {
         const HDRF_GLOBAL uint32_t *p = gptr<uint32_t>(base + apos);
-        // the last 16-B load with a chunk byte in it (end > pos: the window starts inside the chunk)
-        const uint32_t qmax = HDRF_SHA_CLAMP ? (end - 1u - apos) >> 4 : 16u;
+        const uint32_t qmax = 16u;
 #pragma unroll
         for (int q = 0; q < 16; q++) {
             u32x4a v = *(const HDRF_GLOBAL u32x4a *)(p + 4 * min((uint32_t)q, qmax));
             d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
         }
-        d[64] = p[HDRF_SHA_CLAMP ? min(64u, (end - 1u - apos) >> 2) : 64u];
+        d[64] = p[64u];
     } else {
 #pragma unroll
         for (int q = 0; q < 65; q++) d[q] = load4_guard(base, (int64_t)apos + 4 * q, (int64_t)readable);
@@ -393,10 +387,10 @@ hipError_t launch_sha(int hasher, const BlockDesc *d_blocks, int nblocks, const 
         const char *e = getenv("HDRF_SHA_WAVES");
         return 4 * (e ? atoi(e) : 2);
     }();
-    static const int lds = [] { const char *e = getenv("HDRF_SHA_LDS"); return e ? atoi(e) : 0; }();
+    static const int lds = env_int("HDRF_SHA_LDS", 0);
     // HDRF_SHA_CARRY: 1 = sha_carry (4-block windows, the second pair carried in registers; default),
     // 0 = sha_chunk
-    static const bool carryk = [] { const char *e = getenv("HDRF_SHA_CARRY"); return !e || atoi(e) != 0; }();
+    static const bool carryk = env_int("HDRF_SHA_CARRY", 1) != 0;
     const int wpb = std::max(4, (per_cu * 256 / nblocks) & ~3);
     dim3 g(wpb / 4, nblocks + 1);                  // y = 0: the long-chunk lanes
     if (carryk && hasher == 0)

@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(256) flush_kernel(StoreParams P, const BlockSt
 // the first close falls after the last chunk whose stream prefix is <= cmax - x, and from
 // there on every close is fixed by the data.  fn_chain tabulates, for every distinct stream
 // prefix v <= cmax (the possible first-close points), the final container start and the number
-// of closes; the host (api.hip gx_apply_fn) evaluates the function for any x, so the ranks'
+// of closes; the host (api_gx.hip gx_apply_fn) evaluates the function for any x, so the ranks'
 // allocator states come from one all-gather instead of a rank-to-rank chain.
 // grid n_thread x 64: one wave per range, lane = block
 __global__ void __launch_bounds__(64) fn_info_kernel(StoreParams P, const BlockState *__restrict__ bst,
@@ -367,7 +367,7 @@ hipError_t launch_fn_pack(int n_thread, const FnRange *fr, const uint64_t *rows,
     return hipGetLastError();
 }
 
-// The node's allocator through every rank's flush function, rank order (api.hip gx_apply_fn on the
+// The node's allocator through every rank's flush function, rank order (api_gx.hip gx_apply_fn on the
 // device): lane t < n_thread evaluates range t, the ranges are independent.  One wave.
 __global__ void __launch_bounds__(64) gx_scan_kernel(const uint8_t *__restrict__ descs, uint64_t fn_bytes, int G,
                                                      int rank, int n_thread, uint32_t per, uint32_t cmax,
@@ -601,7 +601,7 @@ __global__ void __launch_bounds__(256) place_kernel(StoreParams P, const BlockDe
 int stream_knobs()
 {
     // r02 A/B on the config-2 bench (scripts/ab_nt.txt): 973 / 984 GB/s off, 994 / 995 with both
-    static const int k = [] { const char *e = getenv("HDRF_NT"); return e ? atoi(e) : 3; }();
+    static const int k = env_int("HDRF_NT", 3);
     return k;
 }
 
@@ -696,7 +696,7 @@ __global__ void __launch_bounds__(256) recipe_copy_kernel(const RecipeCopy *__re
     if (t < j.words && blockIdx.y * 256 + threadIdx.x < 4) dst[t] = src[t];
 }
 
-// Container drain (api.hip hdrf_drain_containers) into pinned host memory: the CUs write the bytes
+// Container drain (api_views.hip hdrf_drain_containers) into pinned host memory: the CUs write the bytes
 // straight across PCIe (the host buffer is device-mapped), so the D2H of a DataNode's container files
 // runs beside the SDMA engine's H2D copies of the next blocks instead of queueing behind them.
 // Items (job j, piece y of kXferPiece bytes), numbered y * jobs + j; `wgs` workgroups loop over them

@@ -1,6 +1,6 @@
 """Dirty slack past a block's end (round-4 verdict, weak 1): the 64 readable bytes after every block
-are arbitrary for device batches, and the host paths no longer zero them (hdrf_submit_host,
-hdrf_submit_slots: api.hip).  The granule-max pass folds those bytes into the last partial
+are arbitrary for device batches, and the host paths no longer zero them (hdrf_submit_host: api.hip,
+hdrf_submit_slots: api_rx.hip).  The granule-max pass folds those bytes into the last partial
 granule's maximum (chunk.hip gmax2_kernel), so exactness rests on the walk's raw-byte limits.
 
 Adversarial slack: 0x7F (the largest signed byte: a cut wherever the walk would read it, and the
