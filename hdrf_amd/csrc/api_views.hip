@@ -425,11 +425,43 @@ int host::grow(hdrf_ctx *ctx, uint8_t **p, uint64_t *cap, uint64_t need)
     return 0;
 }
 
-extern "C" int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out,
-                                    int64_t cap)
+// The containers a read can take bytes from, sorted by id: those loaded back from files, then the
+// arena residents (which win on a tie), each with its base and its two bounds.
+void host::readable_list(const hdrf_ctx *ctx, Readable &r)
 {
-    HDRF_LOCK(ctx);
-    if (!ctx || !recipe || recipe_len < 4) return HDRF_E_INVAL;
+    struct One { uint64_t base, alloc; uint32_t valid; };
+    std::map<uint32_t, One> rdbl;
+    for (auto &kv : ctx->loaded)                          // hdrf_container_load: raw + 64 bytes allocated
+        rdbl[kv.first] = One{(uint64_t)(uintptr_t)kv.second.ptr, kv.second.len + 64, (uint32_t)kv.second.len};
+    for (auto &kv : ctx->containers)
+        rdbl[kv.first] = One{(uint64_t)(uintptr_t)(ctx->d_arena + (size_t)kv.second.slot * ctx->cfg.container_max),
+                             ctx->cfg.container_max, kv.second.len};
+    r.cid.clear(); r.base.clear(); r.alloc.clear(); r.valid.clear();
+    for (auto &kv : rdbl) {
+        r.cid.push_back(kv.first);
+        r.base.push_back(kv.second.base);
+        r.alloc.push_back(kv.second.alloc);
+        r.valid.push_back(kv.second.valid);
+    }
+}
+
+static std::string hex_digest(const uint8_t *d, int H)
+{
+    static const char *x = "0123456789abcdef";
+    std::string s;
+    for (int i = 0; i < H; i++) { s += x[d[i] >> 4]; s += x[d[i] & 15]; }
+    return s;
+}
+
+// hdrf_reconstruct (bad_chunk == nullptr) and hdrf_reconstruct_verified: the caller holds the lock.
+// Verified: once the gather ran, every chunk of the rebuilt block is re-hashed on the same stream and
+// compared with its recipe digest (vf_hash, verify.hip), which checks the gather as well as the
+// container bytes.
+static int64_t reconstruct_body(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out, int64_t cap,
+                                int64_t *bad_chunk)
+{
+    const bool verify = bad_chunk != nullptr;
+    if (verify) *bad_chunk = -1;
     if (ctx->G > 1)
         return set_err(ctx, HDRF_E_UNSUPPORTED, "node-global contexts read through hdrf_gx_read_locate / _fill (every rank)");
     if (int rc = drain(ctx)) return rc;
@@ -437,20 +469,18 @@ extern "C" int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_
     const int64_t n = recipe_len / ctx->H;             // t1data.length / hash_length (:223)
     if (size > cap || (size && !dev_out)) return set_err(ctx, HDRF_E_CAPACITY, "output capacity");
     if (n == 0) return size == 0 ? 0 : set_err(ctx, HDRF_E_DEVICE, "recipe without digests");
-    // readable containers sorted by id: arena-resident ones, then those loaded back from files
-    std::map<uint32_t, uint64_t> rdbl;
-    for (auto &kv : ctx->loaded) rdbl[kv.first] = (uint64_t)(uintptr_t)kv.second.ptr;
-    for (auto &kv : ctx->containers)
-        rdbl[kv.first] = (uint64_t)(uintptr_t)(ctx->d_arena + (size_t)kv.second.slot * ctx->cfg.container_max);
-    std::vector<uint32_t> cid;
-    std::vector<uint64_t> base;
-    for (auto &kv : rdbl) { cid.push_back(kv.first); base.push_back(kv.second); }
+    Readable rd;
+    readable_list(ctx, rd);
+    const std::vector<uint32_t> &cid = rd.cid;
+    const std::vector<uint64_t> &base = rd.base;
     const int ncont = (int)cid.size();
     const uint64_t o_dig = 0, dig_b = (uint64_t)n * ctx->HW * 4;
     const uint64_t o_ch = (dig_b + 255) & ~255ull, ch_b = (uint64_t)n * rd_chunk_bytes();
     const uint64_t o_base = (o_ch + ch_b + 255) & ~255ull, base_b = (uint64_t)std::max(1, ncont) * 8;
     const uint64_t o_cid = (o_base + base_b + 255) & ~255ull, cid_b = (uint64_t)std::max(1, ncont) * 4;
     const uint64_t o_tot = (o_cid + cid_b + 255) & ~255ull;
+    const uint64_t o_vf = o_tot + 64;                  // verified: the hash counters, in o_tot's 256 B
+    static_assert(64 + sizeof(VfCounters) <= 256, "the counters share the totals' block");
     if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, o_tot + 256)) return rc;
     uint8_t *R = ctx->d_rd;
     hipStream_t st = ctx->st;
@@ -471,14 +501,50 @@ extern "C" int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_
     if ((int64_t)tot[0] != size) return set_err(ctx, HDRF_E_DEVICE, "chunk lengths do not add up to the recipe size");
     HIPCK(launch_reconstruct(ctx->cfg.hasher, nullptr, (int)n, nullptr, 0, 0, nullptr, bases, 0, R + o_ch, nullptr,
                              dev_out, nullptr, st, true));
+    VfCounters vc{};
+    if (verify) {
+        HIPCK(hipMemsetAsync(R + o_vf, 0, sizeof vc, st));
+        HIPCK(launch_vf_hash_block(ctx->cfg.hasher, R + o_ch, (int)n, (const uint32_t *)(R + o_dig), dev_out,
+                                   (uint64_t)size, (VfCounters *)(R + o_vf), vf_workgroups(ctx), st));
+        HIPCK(hipMemcpyAsync(&vc, R + o_vf, sizeof vc, hipMemcpyDeviceToHost, st));
+    }
     HIPCK(hipStreamSynchronize(st));
+    if (verify && vc.checked != (uint32_t)n) return set_err(ctx, HDRF_E_DEVICE, "verified read: not every chunk was hashed");
+    if (verify && vc.n_bad) {
+        const uint32_t k = ~vc.first_bad_inv;
+        *bad_chunk = k;
+        uint32_t c[4] = {0, 0, 0, 0};                  // RdChunk {readable index, start, len, block offset}
+        HIPCK(hipMemcpy(c, R + o_ch + (uint64_t)k * rd_chunk_bytes(), sizeof c, hipMemcpyDeviceToHost));
+        const std::string where = c[0] < cid.size() ? "container " + std::to_string(cid[c[0]]) : std::string("no container");
+        return set_err(ctx, HDRF_E_CORRUPT,
+                       "recipe position " + std::to_string(k) + ": digest " + hex_digest(recipe + 4 + (size_t)k * ctx->H, ctx->H) +
+                           ", " + where + " [" + std::to_string(c[1]) + ", " + std::to_string(c[1] + c[2]) +
+                           "): the bytes hash to another digest (" + std::to_string(vc.n_bad) + " of " +
+                           std::to_string(n) + " chunks of the block)");
+    }
     return size;
 }
 
-extern "C" int64_t hdrf_reconstruct_block(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap)
+extern "C" int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out,
+                                    int64_t cap)
 {
     HDRF_LOCK(ctx);
-    if (!ctx) return HDRF_E_INVAL;
+    if (!ctx || !recipe || recipe_len < 4) return HDRF_E_INVAL;
+    return reconstruct_body(ctx, recipe, recipe_len, dev_out, cap, nullptr);
+}
+
+extern "C" int64_t hdrf_reconstruct_verified(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out,
+                                             int64_t cap, int64_t *bad_chunk)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !recipe || recipe_len < 4 || !bad_chunk) return HDRF_E_INVAL;
+    return reconstruct_body(ctx, recipe, recipe_len, dev_out, cap, bad_chunk);
+}
+
+// hdrf_reconstruct_block (bad_chunk == nullptr) and hdrf_reconstruct_block_verified
+static int64_t reconstruct_block_body(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap, int64_t *bad_chunk)
+{
+    if (bad_chunk) *bad_chunk = -1;
     if (int rc = drain(ctx)) return rc;
     std::vector<uint8_t> rec;                            // GET longToBytes(blockId,4) (DN/BlockSender.java:292-328)
     const int fr = fetch_recipe(ctx, (uint32_t)block_id, rec);
@@ -487,8 +553,28 @@ extern "C" int64_t hdrf_reconstruct_block(hdrf_ctx *ctx, uint64_t block_id, uint
     const int64_t size = ((int64_t)rec[0] << 24) | (rec[1] << 16) | (rec[2] << 8) | rec[3];
     if (!out || cap < size) return set_err(ctx, HDRF_E_CAPACITY, "needs " + std::to_string(size) + " bytes");
     if (int rc = grow(ctx, &ctx->d_stage, &ctx->stage_cap, (uint64_t)size + 4096)) return rc;
-    const int64_t got = hdrf_reconstruct(ctx, rec.data(), (int64_t)rec.size(), ctx->d_stage, size);
+    const int64_t got = reconstruct_body(ctx, rec.data(), (int64_t)rec.size(), ctx->d_stage, size, bad_chunk);
+    if (got == HDRF_E_CORRUPT) {                         // the block's bytes are in the output anyway
+        const std::string why = ctx->err;
+        if (size) HIPCK(hipMemcpy(out, ctx->d_stage, size, hipMemcpyDeviceToHost));
+        return set_err(ctx, HDRF_E_CORRUPT, "block " + std::to_string(block_id) + ", " + why);
+    }
     if (got < 0) return got;
     if (got) HIPCK(hipMemcpy(out, ctx->d_stage, got, hipMemcpyDeviceToHost));
     return got;
+}
+
+extern "C" int64_t hdrf_reconstruct_block(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    return reconstruct_block_body(ctx, block_id, out, cap, nullptr);
+}
+
+extern "C" int64_t hdrf_reconstruct_block_verified(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap,
+                                                   int64_t *bad_chunk)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !bad_chunk) return HDRF_E_INVAL;
+    return reconstruct_block_body(ctx, block_id, out, cap, bad_chunk);
 }

@@ -1,7 +1,7 @@
 // ctx.hpp — the context behind the C-ABI (include/hdrf.h) and the host functions its translation
 // units share.  Internal: included only by the api*.hip files (api.hip core and batch pipeline,
 // api_rx.hip packet receive, api_stream.hip stream codecs, api_gx.hip node-global phases,
-// api_views.hip views / restore / drain / reconstruction); each of them names in its header comment
+// api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub); each of them names in its header comment
 // the context state it may write.  Everything here but hdrf_ctx itself lives in hdrf::host, hidden
 // from the library's dynamic symbols.
 #pragma once
@@ -381,6 +381,34 @@ int64_t decode_file(hdrf_ctx *ctx, const uint8_t *file, int64_t flen, uint8_t *d
 // api_views.hip
 // a device scratch buffer of at least `need` bytes (contents are not kept when it grows)
 int grow(hdrf_ctx *ctx, uint8_t **p, uint64_t *cap, uint64_t need);
+// The readable containers sorted by id (arena residents, and those loaded back from files where no
+// resident has the id), each with the two bounds a reader must respect: `valid`, the bytes the
+// container holds (ContainerInfo.len / the loaded file's raw length), and `alloc`, the bytes
+// readable from `base` (container_max / raw + 64).
+struct Readable {
+    std::vector<uint32_t> cid, valid;
+    std::vector<uint64_t> base, alloc;
+};
+void readable_list(const hdrf_ctx *ctx, Readable &r);
+// The two test hooks of the scrub / verified reads (verify.hip, api_verify.hip), both read at every
+// call so a test can set them between calls; neither changes a result:
+//   HDRF_VF_WGS            workgroups (4 waves each) of the persistent hash kernel.  Default: 8 waves
+//                          per CU, as the SHA stage runs (4, 6 and 8 measured alike, 12 and 16 slower,
+//                          profiles/scrub_speed_20261020.txt).  A wave reserves 64 items at a time, so
+//                          only a small grid makes the waves of a small store reserve twice:
+//                          tests/test_scrub.py runs with 1.
+//   HDRF_SCRUB_SLICE_LOG2  log2 of the table slots per scrub slice (10..22, default 22), so a small
+//                          table is walked in several slices.
+inline int vf_workgroups(const hdrf_ctx *ctx)
+{
+    const int w = env_int("HDRF_VF_WGS", 0);
+    return w >= 1 ? w : std::max(1, ctx->n_cu * 2);
+}
+constexpr int kScrubSliceLog2 = 22;
+inline int scrub_slice_log2(const hdrf_ctx *ctx)
+{
+    return std::min(ctx->cfg.index_log2, std::min(kScrubSliceLog2, std::max(10, env_int("HDRF_SCRUB_SLICE_LOG2", kScrubSliceLog2))));
+}
 
 }  // namespace host
 }  // namespace hdrf

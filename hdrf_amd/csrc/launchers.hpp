@@ -251,6 +251,41 @@ hipError_t launch_rd_gather(const void *chunks, int n, const uint64_t *bases, ui
 hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                               unsigned long long key, const uint32_t *cids, const uint64_t *bases, int ncont,
                               void *chunks, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather);
+// fingerprint scrub / verified reads (verify.hip).  Counters of one table slice (scrub) or one
+// rebuilt block (verified read), zeroed by the caller before the launches.
+struct VfCounters {
+    uint32_t n_items;        // items vf_collect appended
+    uint32_t cursor;         // next item a vf_hash lane takes
+    uint32_t n_bad;          // bad-list rows (scrub) / failing chunks (verified read)
+    uint32_t skipped;        // live entries whose container is not readable
+    uint32_t entries;        // live entries seen (after the container filter)
+    uint32_t first_bad_inv;  // verified read: ~(lowest failing recipe position), 0 = none
+    uint32_t checked;        // chains hashed and compared
+    uint32_t pad;
+    unsigned long long bytes;   // bytes hashed
+};
+struct VfBadRow {            // the layout of hdrf_bad_chunk
+    uint32_t dig[7];
+    uint32_t cid, start, stop;
+    int32_t why;
+};
+constexpr size_t kVfItemBytes = 16, kVfBadBytes = 8;      // per table slot of a slice: item, bad-list row
+// slots [slot0, slot0 + nslots) of tab: live entries of container `filter` (< 0: all) -> items / bad
+// rows (reason 2) / skipped; cids (sorted) and valid (bytes of each container) describe the readable list
+hipError_t launch_vf_collect(const IndexEntry *tab, uint64_t slot0, uint32_t nslots, unsigned long long key,
+                             int64_t filter, const uint32_t *cids, const uint32_t *valid, int ncont, void *items,
+                             uint32_t *bad, VfCounters *C, int wgs, hipStream_t st);
+// hash the collected items (C->n_items, read on the device) against their entries; allocs: bytes
+// readable from each container's base; wgs workgroups of persistent waves
+hipError_t launch_vf_hash_items(int hasher, const void *items, const IndexEntry *tab, uint64_t slot0,
+                                const uint64_t *bases, const uint64_t *allocs, uint32_t *bad, VfCounters *C, int wgs,
+                                hipStream_t st);
+// hash the n chunks (RdChunk rows of launch_reconstruct) of a rebuilt block of block_bytes bytes
+// against the recipe digests dig
+hipError_t launch_vf_hash_block(int hasher, const void *chunks, int n, const uint32_t *dig, const uint8_t *block,
+                                uint64_t block_bytes, VfCounters *C, int wgs, hipStream_t st);
+hipError_t launch_vf_rows(int hasher, const uint32_t *bad, uint32_t from, uint32_t n, const IndexEntry *tab,
+                          uint64_t slot0, VfBadRow *out, hipStream_t st);
 hipError_t launch_corpus(uint8_t *dev, const uint32_t *d_roots, int64_t nblocks, int64_t spb, int64_t seg_bytes,
                          uint64_t seed, int mixed, hipStream_t st);
 

@@ -47,41 +47,8 @@ __device__ __forceinline__ void load_win65(const uint8_t *base, uint64_t readabl
     }
 }
 
-__device__ __forceinline__ bool pair_at(uint32_t bi, uint32_t T) { return bi < T && ((T - bi) & 1u); }
-
-// The compressions of one iteration from a loaded window (see sha_iter).
-template <int HW>
-__device__ __forceinline__ void sha_compute(const uint32_t d[33], uint32_t pos, uint32_t len, uint32_t T, uint32_t nb,
-                                            uint32_t bi, bool two, uint32_t st[8])
-{
-    const uint32_t sel = 0x00010203u + (pos & 3u) * 0x01010101u;
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) m[i] = __builtin_amdgcn_perm(d[i + 1], d[i], sel);
-    if (ballot64(bi >= T)) pad_block(m, len, bi, nb);
-    if (HW == 5) sha1_compress(st, m);
-    else sha256_compress(st, m);
-    if (two) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) m[i] = __builtin_amdgcn_perm(d[i + 17], d[i + 16], sel);
-        if (ballot64(bi + 1 == T)) pad_block(m, len, bi + 1, nb);
-        if (HW == 5) sha1_compress(st, m);
-        else sha256_compress(st, m);
-    }
-}
-
-template <int HW>
-__device__ __forceinline__ void sha_iter(const uint8_t *base, uint64_t readable, uint32_t s0, uint32_t len, uint32_t T,
-                                         uint32_t nb, uint32_t &bi, uint32_t st[8])
-{
-    const bool two = pair_at(bi, T);
-    const uint32_t pos = s0 + 64u * bi;
-    uint32_t d[33];
-    load_win(base, readable, pos, two, d);
-    sha_compute<HW>(d, pos, len, T, nb, bi, two, st);
-    bi += two ? 2u : 1u;
-}
-
+// (pair_at, sha_compute and sha_iter, one iteration of a lane's chain, are in sha_core.hpp: the
+// scrub's hash kernel in verify.hip runs the same chain)
 template <int HW>
 __device__ __forceinline__ void store_digest(uint32_t *dst, const uint32_t st[8])
 {

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("HDRF_LIB_PATH") or os.path.join(_HERE, "_build", "lib
 
 HDRF_ERRORS = {
     -1: "HDRF_E_INVAL", -2: "HDRF_E_HIP", -3: "HDRF_E_NOMEM", -4: "HDRF_E_CAPACITY",
-    -5: "HDRF_E_NOTFOUND", -6: "HDRF_E_UNSUPPORTED", -7: "HDRF_E_DEVICE",
+    -5: "HDRF_E_NOTFOUND", -6: "HDRF_E_UNSUPPORTED", -7: "HDRF_E_DEVICE", -8: "HDRF_E_CORRUPT",
 }
 
 # every symbol include/hdrf.h declares (checked by tests/test_abi.py)
@@ -36,6 +36,7 @@ EXPORTS = [
     "hdrf_gx_read_locate", "hdrf_gx_read_fill", "hdrf_gx_flush_fn", "hdrf_gx_alloc_scan",
     "hdrf_set_lzop_mtime", "hdrf_gx_flush_fn_dev", "hdrf_gx_alloc_scan_dev", "hdrf_gx_place_launch",
     "hdrf_gx_place_wait", "hdrf_gx_sync", "hdrf_reset_async",
+    "hdrf_scrub", "hdrf_reconstruct_verified", "hdrf_reconstruct_block_verified",
 ]
 
 ALLOC_STATE_BYTES = 128     # HDRF_ALLOC_STATE_BYTES
@@ -56,9 +57,10 @@ STAGES = ["walk(lane_walk_kernel)", "stitch(repair/path/count/scan/copy/fallback
 
 
 class HdrfError(RuntimeError):
-    def __init__(self, code, msg):
+    def __init__(self, code, msg, bad_chunk=None):
         super().__init__(f"{HDRF_ERRORS.get(code, code)}: {msg}")
         self.code = code
+        self.bad_chunk = bad_chunk      # HDRF_E_CORRUPT of a verified read: the lowest failing recipe position
 
 
 class Config(ctypes.Structure):
@@ -81,6 +83,15 @@ class ContainerEvent(ctypes.Structure):
 class Stats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("blocks", "chunks", "logical_bytes", "new_bytes", "closed_containers",
                                              "closed_raw_bytes", "closed_file_bytes", "open_bytes", "recipe_bytes")]
+
+
+class BadChunk(ctypes.Structure):           # hdrf_bad_chunk (44 B)
+    _fields_ = [("digest", ctypes.c_uint8 * 28), ("container", ctypes.c_uint32), ("start", ctypes.c_uint32),
+                ("stop", ctypes.c_uint32), ("why", ctypes.c_int32)]
+
+
+class ScrubStats(ctypes.Structure):         # hdrf_scrub_stats (40 B)
+    _fields_ = [(n, ctypes.c_int64) for n in ("entries", "checked", "skipped", "bytes", "bad")]
 
 
 class GxLayout(ctypes.Structure):
@@ -165,6 +176,10 @@ def load():
         "hdrf_batch_nblocks": (ctypes.c_int, [_vp]),
         "hdrf_reconstruct": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp, ctypes.c_int64]),
         "hdrf_reconstruct_block": (ctypes.c_int64, [_vp, ctypes.c_uint64, _u8p, ctypes.c_int64]),
+        "hdrf_reconstruct_verified": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp, ctypes.c_int64, _i64p]),
+        "hdrf_reconstruct_block_verified": (ctypes.c_int64, [_vp, ctypes.c_uint64, _u8p, ctypes.c_int64, _i64p]),
+        "hdrf_scrub": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.POINTER(BadChunk), ctypes.c_int64,
+                                        ctypes.POINTER(ScrubStats)]),
         "hdrf_gx_read_locate": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp]),
         "hdrf_gx_flush_fn": (ctypes.c_int64, [_vp, _vp, ctypes.c_int64]),
         "hdrf_gx_alloc_scan": (ctypes.c_int32, [_vp, _vp, _vp, _u8p, _u8p]),
@@ -544,16 +559,52 @@ class Context:
         m = self._ck(self.L.hdrf_recipe_get(self._h, block_id, _p(out), need))
         return out[:m].tobytes()
 
-    def reconstruct_block(self, block_id):
-        """DataConstructor(blkID, recipe).data: the block rebuilt from the index + containers."""
+    def _ck_verified(self, rc, bad):
+        if rc == -8:                        # HDRF_E_CORRUPT
+            raise HdrfError(rc, self.L.hdrf_last_error(self._h).decode(), bad_chunk=bad.value)
+        return self._ck(rc)
+
+    def reconstruct_block(self, block_id, verify=False):
+        """DataConstructor(blkID, recipe).data: the block rebuilt from the index + containers.
+        verify=True: every chunk of the rebuilt block is re-hashed and compared with its recipe digest;
+        a mismatch raises HdrfError (code -8, .bad_chunk = the lowest failing recipe position)."""
         n = self.block_length(block_id)
         out = np.zeros(max(n, 1), np.uint8)
+        if verify:
+            bad = ctypes.c_int64(-1)
+            m = self._ck_verified(self.L.hdrf_reconstruct_block_verified(self._h, block_id, _p(out), n,
+                                                                         ctypes.byref(bad)), bad)
+            return out[:m]
         m = self._ck(self.L.hdrf_reconstruct_block(self._h, block_id, _p(out), n))
         return out[:m]
 
-    def reconstruct(self, recipe, dev_out, cap):
+    def reconstruct(self, recipe, dev_out, cap, verify=False):
         r = np.frombuffer(bytes(recipe), np.uint8).copy()
+        if verify:
+            bad = ctypes.c_int64(-1)
+            return self._ck_verified(self.L.hdrf_reconstruct_verified(self._h, _p(r), r.size, dev_out, cap,
+                                                                      ctypes.byref(bad)), bad)
         return self._ck(self.L.hdrf_reconstruct(self._h, _p(r), r.size, dev_out, cap))
+
+    def scrub(self, container=None):
+        """hdrf_scrub: every index entry whose container is readable re-hashed from the container's
+        bytes and compared with its key (container=None: all readable containers).  Returns
+        (stats, bad) with stats = dict(entries, checked, skipped, bytes, bad) and bad = the bad chunks
+        sorted by (container, start, digest): dict(digest, container, start, stop, why) each; why 1:
+        the bytes hash to another digest, 2: [start, stop) is not inside the container's bytes."""
+        cid = -1 if container is None else int(container)
+        cap = 256
+        while True:
+            buf = (BadChunk * cap)()
+            st = ScrubStats()
+            n = self._ck(self.L.hdrf_scrub(self._h, cid, buf, cap, ctypes.byref(st)))
+            if n > cap:
+                cap = n
+                continue
+            stats = {f: getattr(st, f) for f, _ in ScrubStats._fields_}
+            bad = [dict(digest=bytes(b.digest[:self.H]), container=b.container, start=b.start, stop=b.stop, why=b.why)
+                   for b in buf[:n]]
+            return stats, bad
 
     def block_length(self, block_id):
         return self._ck(self.L.hdrf_block_length(self._h, block_id))

@@ -42,8 +42,15 @@ class HipReductionScheme(ReductionScheme):
         self.last = self.ctx.reduce_block(block, block_id)
         return self.last
 
-    def reconstruct(self, block_id):
+    def reconstruct(self, block_id, verify=False):
+        """verify=True: every chunk re-hashed against its recipe digest (HdrfError -8 on a mismatch)."""
+        if verify:
+            return self.ctx.reconstruct_block(block_id, verify=True).tobytes()
         return self.ctx.reconstruct_block(block_id).tobytes()
+
+    def scrub(self, container=None):
+        """Re-hash every stored chunk whose container is readable: (stats, bad chunks)."""
+        return self.ctx.scrub(container)
 
     def length(self, block_id):
         return self.ctx.block_length(block_id)

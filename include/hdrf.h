@@ -32,6 +32,7 @@ extern "C" {
 #define HDRF_E_NOTFOUND (-5)   /* key / block / container absent */
 #define HDRF_E_UNSUPPORTED (-6)/* option not implemented in this build */
 #define HDRF_E_DEVICE (-7)     /* a kernel reported an inconsistency */
+#define HDRF_E_CORRUPT (-8)    /* stored bytes do not hash to their fingerprint */
 
 typedef struct hdrf_ctx hdrf_ctx;
 
@@ -282,6 +283,38 @@ int hdrf_reduce_block_ticketed(hdrf_ctx *ctx, uint64_t ticket, uint64_t block_id
 int64_t hdrf_reconstruct(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out, int64_t cap);
 int64_t hdrf_reconstruct_block(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap);
 
+/* Fingerprint scrub and verified reads.  The store is content-addressed: every chunk's index key is
+ * the SHA-1 / SHA-224 of its bytes, so stored bytes can be checked against the key that names them
+ * (what the DataNode block scanner and the checksums of an HDFS read do for block files). */
+typedef struct {
+    uint8_t  digest[28];        /* the index key (first digest_len bytes) */
+    uint32_t container, start, stop;
+    int32_t  why;               /* 1: bytes hash to another digest; 2: [start, stop) not inside the container's bytes */
+} hdrf_bad_chunk;
+
+typedef struct {
+    int64_t entries;            /* live index entries seen (after the container filter) */
+    int64_t checked;            /* hashed and compared */
+    int64_t skipped;            /* container neither arena-resident nor loaded */
+    int64_t bytes;              /* bytes hashed */
+    int64_t bad;                /* == the return value */
+} hdrf_scrub_stats;
+
+/* Scrub: every index entry whose container is readable (arena-resident, or loaded with
+ * hdrf_container_load) is re-hashed from the container's bytes and compared with its key.
+ * container = -1: all readable containers; otherwise that id (HDRF_E_NOTFOUND if not readable).
+ * Returns the number of bad chunks; the first min(bad, cap) are written sorted by
+ * (container, start, digest).  A view: completes the batches in flight first.  Single-node contexts. */
+int64_t hdrf_scrub(hdrf_ctx *ctx, int64_t container, hdrf_bad_chunk *bad, int64_t cap, hdrf_scrub_stats *st);
+
+/* hdrf_reconstruct / hdrf_reconstruct_block, then every chunk of the rebuilt block re-hashed and
+ * compared with its recipe digest.  Returns the block size, or HDRF_E_CORRUPT with *bad_chunk = the
+ * lowest recipe position that failed (the block's bytes are in the output anyway; hdrf_last_error
+ * names the digest, the container and the range).  *bad_chunk = -1 otherwise. */
+int64_t hdrf_reconstruct_verified(hdrf_ctx *ctx, const uint8_t *recipe, int64_t recipe_len, uint8_t *dev_out,
+                                  int64_t cap, int64_t *bad_chunk);
+int64_t hdrf_reconstruct_block_verified(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap, int64_t *bad_chunk);
+
 /* The same read on a node-global context (cfg.n_ranks = G > 1): the node's ONE index is
  * partitioned over the ranks, and a container's bytes are spread over the ranks that placed
  * chunks into it, so every rank takes part (hdrf_amd/node.py NodeRank.reconstruct_block; the
@@ -349,7 +382,7 @@ int hdrf_reset(hdrf_ctx *ctx);
  * DataNode, so its front half overlaps the old batches' back halves.  Node-global contexts make the
  * switch in that batch's hdrf_gx_owner (the old batches' owner phases, enqueued after this call, still
  * use the old index epoch) and reset the host side in its hdrf_gx_place_wait.  Views and restores (hdrf_index_*, hdrf_*_load, reconstruct, container
- * reads, hdrf_synchronize) complete every batch first, as always, and a reset still pending then (no
+ * reads, hdrf_scrub, hdrf_synchronize) complete every batch first, as always, and a reset still pending then (no
  * submit since) is applied before they run, so they see the fresh DataNode and a restore is kept.
  * cfg.retain_containers: drain the old batches' containers as they complete (hdrf_wait_batch,
  * hdrf_drain_containers); while any old container (closed, or bytes of an open one) is not handed

@@ -101,6 +101,34 @@ class HipReductionScheme final : public ReductionScheme {
         return out;
     }
 
+    // reconstruct with every chunk of the rebuilt block re-hashed against its recipe digest:
+    // throws Error(HDRF_E_CORRUPT) naming the digest, the container and the range
+    std::vector<uint8_t> reconstruct_verified(uint64_t block_id)
+    {
+        const int64_t len = hdrf_block_length(ctx_, block_id);
+        if (len < 0) check((int)len);
+        std::vector<uint8_t> out((size_t)len);
+        int64_t bad = -1;
+        const int64_t n = hdrf_reconstruct_block_verified(ctx_, block_id, out.data(), len, &bad);
+        if (n < 0) check((int)n);
+        out.resize((size_t)n);
+        return out;
+    }
+
+    // every index entry whose container is readable re-hashed against its key: the bad chunks
+    // (sorted by container, start, digest) and, when st is given, the counts
+    std::vector<hdrf_bad_chunk> scrub(int64_t container = -1, hdrf_scrub_stats *st = nullptr)
+    {
+        std::vector<hdrf_bad_chunk> bad(64);
+        for (;;) {
+            const int64_t n = hdrf_scrub(ctx_, container, bad.data(), (int64_t)bad.size(), st);
+            if (n < 0) check((int)n);
+            const bool fits = n <= (int64_t)bad.size();
+            bad.resize((size_t)n);
+            if (fits) return bad;
+        }
+    }
+
     int64_t length(uint64_t block_id) override
     {
         int64_t n = hdrf_block_length(ctx_, block_id);

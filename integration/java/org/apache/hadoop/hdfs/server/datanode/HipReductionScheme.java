@@ -158,6 +158,23 @@ public final class HipReductionScheme extends ReductionScheme {
     return reconstruct0(ctx, blockId);          // DataConstructor(blkID, recipe).data
   }
 
+  /**
+   * reconstruct with every chunk of the rebuilt block re-hashed against its recipe digest (what
+   * BlockSender calls): IOException naming the digest, the container and the range when stored
+   * bytes no longer hash to their fingerprint.
+   */
+  public byte[] reconstructVerified(long blockId) throws IOException {
+    return reconstructVerified0(ctx, blockId);
+  }
+
+  /**
+   * The block scanner: every index entry whose container is resident or loaded is re-hashed from
+   * the container's bytes and compared with its key; returns the number of bad chunks.
+   */
+  public long scrub() throws IOException {
+    return scrub0(ctx);
+  }
+
   @Override
   public long length(long blockId) throws IOException {
     return length0(ctx, blockId);
@@ -176,6 +193,8 @@ public final class HipReductionScheme extends ReductionScheme {
   private static native long open0(int hasher, int compressor, int device, long maxBlockBytes, int maxBatchBlocks)
       throws IOException;
   private static native byte[] reconstruct0(long ctx, long blockId) throws IOException;
+  private static native byte[] reconstructVerified0(long ctx, long blockId) throws IOException;
+  private static native long scrub0(long ctx) throws IOException;
   private static native void reduce0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void submit0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void wait0(long ctx) throws IOException;

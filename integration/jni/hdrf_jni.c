@@ -277,6 +277,37 @@ JNIEXPORT jbyteArray JNICALL JFN(reconstruct0)(JNIEnv *env, jclass cls, jlong h,
     return out;
 }
 
+/* The same with every chunk of the rebuilt block re-hashed against its recipe digest: what
+ * BlockSender calls when the read must not return bytes that differ from what was written
+ * (HDRF_E_CORRUPT -> IOException naming the digest, the container and the range). */
+JNIEXPORT jbyteArray JNICALL JFN(reconstructVerified0)(JNIEnv *env, jclass cls, jlong h, jlong id)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int64_t len = hdrf_block_length(ctx, (uint64_t)id);
+    if (len < 0) { throw_io(env, ctx, (int)len); return NULL; }
+    uint8_t *tmp = (uint8_t *)malloc((size_t)(len ? len : 1));
+    if (!tmp) { throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+    int64_t bad = -1;
+    int64_t n = hdrf_reconstruct_block_verified(ctx, (uint64_t)id, tmp, len, &bad);
+    if (n < 0) { free(tmp); throw_io(env, ctx, (int)n); return NULL; }
+    jbyteArray out = (*env)->NewByteArray(env, (jsize)n);
+    if (out) (*env)->SetByteArrayRegion(env, out, 0, (jsize)n, (const jbyte *)tmp);
+    free(tmp);
+    return out;
+}
+
+/* The block scanner of a content-addressed store: every index entry whose container is readable
+ * re-hashed against its key; returns how many are bad (hdrf_scrub). */
+JNIEXPORT jlong JNICALL JFN(scrub0)(JNIEnv *env, jclass cls, jlong h)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int64_t n = hdrf_scrub(ctx, -1, NULL, 0, NULL);
+    if (n < 0) throw_io(env, ctx, (int)n);
+    return (jlong)n;
+}
+
 /* stream mode (compressor 0 SnappyCodec / 3 LzopCodec / 4 Lz4Codec / 5 GzipCodec): the block's chunkDir
  * file for packet writes.  LzopCodec headers carry the wall clock, as LzopOutputStream writes
  * System.currentTimeMillis() / 1000. */
