@@ -662,6 +662,37 @@ static uint32_t close_bound(const hdrf_cfg &c, uint64_t bytes)
     return (uint32_t)std::min<uint64_t>(std::min(a, b), 1u << 30) + 1;
 }
 
+// The front of a batch, as the single-GPU submit and the node-global front launch both enqueue it:
+// the descriptors go up on G (after the packet copies when after_copy), chunking runs on W (its granule
+// pass on G), then the fingerprints on A once the walk is done and the recipe copies of the slot's
+// previous batch have read d_dig.  fused: the fused front writes d_dig on W already, so W waits for
+// those copies too, and the SHA pass takes only the chunks marked in d_need (each block's last one,
+// repairs, fallbacks).  mw / ma: the stage markers of W and A.
+int host::enqueue_front(hdrf_ctx *ctx, Slot &S, int nblocks, hipStream_t W, hipStream_t G, hipStream_t A, Marker *mw,
+                        Marker *ma, bool after_copy, bool fused)
+{
+    const hdrf_cfg &c = ctx->cfg;
+    if (after_copy) HIPCK(hipStreamWaitEvent(G, S.copy_done, 0));
+    HIPCK(hipMemcpyAsync(S.d_blocks, S.h_desc, sizeof(BlockDesc) * nblocks, hipMemcpyHostToDevice, G));
+    if (fused && S.recipe_pending) HIPCK(hipStreamWaitEvent(W, S.recipe_done, 0));
+    const FusedFront fz{c.hasher, S.d_sdig, S.d_bdig, S.d_dig, S.d_need, S.d_gmneed};
+    HIPCK(launch_chunking(S.d_blocks, nblocks, S.max_len, S.max_nseg, S.total_waves, S.total_segs,
+                          chunk_scratch(S, c.compressor), c.window, c.max_chunk, S.d_spec, S.spec_cap, S.d_meta, S.d_bst,
+                          S.d_off, ctx->cap_blk, S.d_err, W, mw, G, S.gmax_done, fused ? &fz : nullptr));
+    mw->mark(W);
+    HIPCK(hipEventRecord(S.walk_done, W));
+    HIPCK(hipStreamWaitEvent(A, S.walk_done, 0));
+    if (S.recipe_pending) HIPCK(hipStreamWaitEvent(A, S.recipe_done, 0));
+    if (fused)
+        HIPCK(launch_sha_need(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, S.d_need,
+                              S.d_nlist, A, ma));
+    else
+        HIPCK(launch_sha(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, ctx->sha_long, A,
+                         ma));
+    ma->mark(A);
+    return 0;
+}
+
 // Enqueue one batch: front on stream A, back on stream B (see the file comment).
 int host::submit(hdrf_ctx *ctx, int32_t nblocks, const uint8_t *const *dev_data, const uint64_t *len,
                  const uint64_t *readable, const uint64_t *block_ids, bool after_copy)
@@ -709,33 +740,12 @@ int host::submit(hdrf_ctx *ctx, int32_t nblocks, const uint8_t *const *dev_data,
     // runs while W walks and stitches this one (latency-bound)
     static const bool gstream = env_int("HDRF_GMAX_STREAM", 0) != 0;
     hipStream_t G = gstream ? ctx->stG : W;
-    // ---- chunking on W: the slot's previous batch has completed (wait_one ran), so W may overwrite it
-    if (after_copy) HIPCK(hipStreamWaitEvent(G, S.copy_done, 0));
-    HIPCK(hipMemcpyAsync(S.d_blocks, S.h_desc, sizeof(BlockDesc) * nblocks, hipMemcpyHostToDevice, G));
-    Marker mw;
+    // ---- chunking on W (the slot's previous batch has completed: wait_one ran, so W may overwrite it),
+    // fingerprints on A
+    Marker mw, ma;
     mw.ev = ctx->timing ? S.evW : nullptr;
-    // (the fused front writes d_dig on W: after the recipe copies of the slot's previous batch read it)
-    const bool fz_on = ctx->fused;
-    if (fz_on && S.recipe_pending) HIPCK(hipStreamWaitEvent(W, S.recipe_done, 0));
-    const FusedFront fz{c.hasher, S.d_sdig, S.d_bdig, S.d_dig, S.d_need, S.d_gmneed};
-    HIPCK(launch_chunking(S.d_blocks, nblocks, S.max_len, S.max_nseg, S.total_waves, S.total_segs,
-                          chunk_scratch(S, c.compressor), c.window, c.max_chunk, S.d_spec, S.spec_cap, S.d_meta, S.d_bst,
-                          S.d_off, ctx->cap_blk, S.d_err, W, &mw, G, S.gmax_done, fz_on ? &fz : nullptr));
-    mw.mark(W);
-    HIPCK(hipEventRecord(S.walk_done, W));
-    // ---- fingerprints on A (after the recipe copies of the slot's previous batch read d_dig); the fused
-    // front leaves only the chunks marked in d_need (each block's last one, repairs, fallbacks)
-    HIPCK(hipStreamWaitEvent(A, S.walk_done, 0));
-    if (S.recipe_pending) HIPCK(hipStreamWaitEvent(A, S.recipe_done, 0));
-    Marker ma;
     ma.ev = ctx->timing ? S.evA : nullptr;
-    if (fz_on)
-        HIPCK(launch_sha_need(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, S.d_need,
-                              S.d_nlist, A, &ma));
-    else
-        HIPCK(launch_sha(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, ctx->sha_long, A,
-                         &ma));
-    ma.mark(A);
+    if (int rc = enqueue_front(ctx, S, nblocks, W, G, A, &mw, &ma, after_copy, ctx->fused)) return rc;
     HIPCK(hipEventRecord(S.front_done, A));
     // ---- back, index part, in block order on stream B: claim .. decide, then idx_finalize takes the
     // batch-local state out of the index (designated chunks, block counts, entries cleared), so the

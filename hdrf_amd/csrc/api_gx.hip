@@ -120,21 +120,11 @@ extern "C" int hdrf_gx_front_launch(hdrf_ctx *ctx, int32_t nblocks, const uint8_
     }
     if (int rc = prepare_blocks(ctx, S, nblocks, dev_data, len, readable)) return rc;
     S.gx_batch = ++ctx->batch;
-    HIPCK(hipMemcpyAsync(S.d_blocks, S.h_desc, sizeof(BlockDesc) * nblocks, hipMemcpyHostToDevice, W));
     GxTime &T = ctx->gxt[seq % kGxRing];
     Marker mw, ma, mx;
     mw.ev = ctx->timing ? &T.ev[kW0] : nullptr;
-    HIPCK(launch_chunking(S.d_blocks, nblocks, S.max_len, S.max_nseg, S.total_waves, S.total_segs,
-                          chunk_scratch(S, c.compressor), c.window, c.max_chunk, S.d_spec, S.spec_cap, S.d_meta, S.d_bst,
-                          S.d_off, ctx->cap_blk, S.d_err, W, &mw));
-    mw.mark(W);
-    HIPCK(hipEventRecord(S.walk_done, W));
-    HIPCK(hipStreamWaitEvent(A, S.walk_done, 0));
-    if (S.recipe_pending) HIPCK(hipStreamWaitEvent(A, S.recipe_done, 0));
     ma.ev = ctx->timing ? &T.ev[kA0] : nullptr;
-    HIPCK(launch_sha(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, ctx->sha_long, A,
-                     &ma));
-    ma.mark(A);
+    if (int rc = enqueue_front(ctx, S, nblocks, W, W, A, &mw, &ma)) return rc;
     HIPCK(hipEventRecord(S.idx_done, A));               // (node-global: "the batch's digests are ready")
     // local aggregation: a fresh scratch table (the next epoch of the slot's table, cleared every 255
     // uses), every entry "created" in batch 1

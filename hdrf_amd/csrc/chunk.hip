@@ -1454,6 +1454,37 @@ int setprio_mask()
     return m;
 }
 
+// The back of both fronts: repair (count), stitch path / count / scan / copy, repair (emit), sequential
+// fallback.  gm: the granule maxima the repair walk and the fallback skip by (nullptr: none were
+// computed); fz: the fused front's digests, carried by the stitch copy and the fallback.
+// 2048 repair waves loop over the queue, one per workgroup: the chain's small kernels start in
+// whatever wave slots the co-running kernels leave (a 4-wave workgroup needs four on one CU)
+static hipError_t launch_repair_stitch(const BlockDesc *d_blocks, int nblocks, const ChunkScratch &X, int w, int maxlen,
+                                       uint32_t *spec, int spec_cap, SegMeta *meta, BlockState *bst, uint32_t *offsets,
+                                       int cap_blk, int *err, hipStream_t st, int maxw, int prio, const uint8_t *gm,
+                                       const FusedFront *fz)
+{
+    const int rgrid = 2048;
+    const int p1 = (prio >> 1) & 1;
+    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
+                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, gm, X.gstride, 0, p1, X.rqkeep);
+    hipLaunchKernelGGL(stitch_path_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.irr, meta, X.path, X.jx, X.jt, X.jcap,
+                       p1);
+    hipLaunchKernelGGL(stitch_count_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, X.path, X.jx, X.jt, X.jcap,
+                       X.wgsum, maxw, err);
+    hipLaunchKernelGGL(stitch_scan_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.path, X.wgsum, maxw, bst,
+                       cap_blk, err);
+    hipLaunchKernelGGL(stitch_copy_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, spec, spec_cap,
+                       X.wgsum, maxw, bst, offsets, cap_blk, fz ? (const uint32_t *)fz->sdig : nullptr,
+                       fz ? (const uint32_t *)fz->bdig : nullptr, fz ? fz->dig : nullptr, fz ? fz->need : nullptr,
+                       fz ? (fz->hasher == 0 ? 5 : 7) : 0);
+    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
+                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, gm, X.gstride, 1, p1, X.rqkeep);
+    hipLaunchKernelGGL(spec_fallback_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, w, maxlen, offsets,
+                       cap_blk, bst, gm, X.gstride, err, p1, fz ? fz->need : nullptr);
+    return hipGetLastError();
+}
+
 // The fused front (HDRF_FUSED=1): lanehash.hip's pass cuts and hashes the lane segments; the granule
 // maxima are computed only when a boundary was queued for the repair walk (whose long searches and the
 // sequential fallback read them); then the stitch as in the two-pass front, carrying the digests.
@@ -1486,24 +1517,8 @@ static hipError_t launch_fused_front(const BlockDesc *d_blocks, int nblocks, int
         hipLaunchKernelGGL((gmax2_kernel<true, true>), dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, st, d_blocks, X.gm,
                            X.gstride, (prio >> 4) & 1, (const int *)fz.gm_need);
     }
-    const int rgrid = 2048;                            // single-wave workgroups (below)
-    const int HW = fz.hasher == 0 ? 5 : 7;
-    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
-                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, gm, X.gstride, 0, (prio >> 1) & 1, X.rqkeep);
-    hipLaunchKernelGGL(stitch_path_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.irr, meta, X.path, X.jx, X.jt, X.jcap,
-                       (prio >> 1) & 1);
-    hipLaunchKernelGGL(stitch_count_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, X.path, X.jx, X.jt, X.jcap,
-                       X.wgsum, maxw, err);
-    hipLaunchKernelGGL(stitch_scan_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.path, X.wgsum, maxw, bst,
-                       cap_blk, err);
-    hipLaunchKernelGGL(stitch_copy_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, spec, spec_cap,
-                       X.wgsum, maxw, bst, offsets, cap_blk, (const uint32_t *)fz.sdig, (const uint32_t *)fz.bdig,
-                       fz.dig, fz.need, HW);
-    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
-                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, gm, X.gstride, 1, (prio >> 1) & 1, X.rqkeep);
-    hipLaunchKernelGGL(spec_fallback_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, w, maxlen, offsets,
-                       cap_blk, bst, gm, X.gstride, err, (prio >> 1) & 1, fz.need);
-    return hipGetLastError();
+    return launch_repair_stitch(d_blocks, nblocks, X, w, maxlen, spec, spec_cap, meta, bst, offsets, cap_blk, err, st, maxw,
+                                prio, gm, &fz);
 }
 
 hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_len, int max_nseg, int total_waves,
@@ -1556,23 +1571,7 @@ hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_l
     hipLaunchKernelGGL(lane_walk_kernel<false>, dim3((total_waves + 3) / 4), dim3(256), walk_lds, st, d_blocks, nblocks, total_waves,
                        X.gm, X.gstride, w, maxlen, spec, spec_cap, meta, X.rq, X.rq_count, X.rq_cap, X.irr, err, ring_on, prio & 1);
     mk->mark(st);
-    // 2048 repair waves loop over the queue, one per workgroup: the chain's small kernels start in
-    // whatever wave slots the co-running kernels leave (a 4-wave workgroup needs four on one CU)
-    const int rgrid = 2048;
-    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
-                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, X.gm, X.gstride, 0, (prio >> 1) & 1, X.rqkeep);
-    hipLaunchKernelGGL(stitch_path_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.irr, meta, X.path, X.jx, X.jt, X.jcap,
-                       (prio >> 1) & 1);
-    hipLaunchKernelGGL(stitch_count_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, X.path, X.jx, X.jt, X.jcap,
-                       X.wgsum, maxw, err);
-    hipLaunchKernelGGL(stitch_scan_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.path, X.wgsum, maxw, bst,
-                       cap_blk, err);
-    hipLaunchKernelGGL(stitch_copy_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, spec, spec_cap,
-                       X.wgsum, maxw, bst, offsets, cap_blk);
-    hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
-                       w, maxlen, spec, spec_cap, meta, offsets, cap_blk, X.gm, X.gstride, 1, (prio >> 1) & 1, X.rqkeep);
-    hipLaunchKernelGGL(spec_fallback_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, w, maxlen, offsets,
-                       cap_blk, bst, X.gm, X.gstride, err, (prio >> 1) & 1);
-    return hipGetLastError();
+    return launch_repair_stitch(d_blocks, nblocks, X, w, maxlen, spec, spec_cap, meta, bst, offsets, cap_blk, err, st, maxw,
+                                prio, X.gm, nullptr);
 }
 }  // namespace hdrf

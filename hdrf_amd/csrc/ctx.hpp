@@ -364,6 +364,10 @@ ChunkScratch chunk_scratch(Slot &S, int compressor = 1);
 int prepare_blocks(hdrf_ctx *ctx, Slot &S, int32_t nblocks, const uint8_t *const *dev_data, const uint64_t *len,
                    const uint64_t *readable);
 StoreParams store_params(const hdrf_ctx *ctx, int nblocks);
+// the front of a batch (single-GPU and node-global alike): descriptors up on G, chunking on W,
+// fingerprints on A; fused: the fused chunk + fingerprint front
+int enqueue_front(hdrf_ctx *ctx, Slot &S, int nblocks, hipStream_t W, hipStream_t G, hipStream_t A, Marker *mw, Marker *ma,
+                  bool after_copy = false, bool fused = false);
 // enqueue one batch: front on stream A, back on stream B
 int submit(hdrf_ctx *ctx, int32_t nblocks, const uint8_t *const *dev_data, const uint64_t *len,
            const uint64_t *readable, const uint64_t *block_ids, bool after_copy = false);

@@ -22,6 +22,7 @@
 //   X3      all-to-all of those locations; owners commit them                        [own_commit]
 #include <algorithm>
 
+#include "index_probe.hpp"
 #include "launchers.hpp"
 
 namespace hdrf {
@@ -92,18 +93,31 @@ __global__ void __launch_bounds__(256) gx_emit_kernel(const BlockState *__restri
 }
 
 // ---- owner side: grid (ceil(cap/256), G) over the records received from each source ------
-// IndexEntry fields during a batch: first = max over records of ~gpos (-> min block), mask =
-// sum of counts (-> blocks holding the digest this batch); both reset by own_finish.
-__device__ __forceinline__ void own_record(IndexEntry *e, uint32_t gpos, uint32_t cnt)
-{
-    atomicMax(&e->first, (unsigned long long)(0xffffffffu - gpos));
-    atomicAdd(&e->mask, (unsigned long long)cnt);
-}
+// The owner's partition runs the claim / apply / slow protocol of index_probe.hpp over the X1
+// records.  The record policy of one record {digest, gpos, cnt} (p = its last two words): IndexEntry
+// fields during a batch: first = max over records of ~gpos (-> min block), mask = sum of counts
+// (-> blocks holding the digest this batch); both reset by own_finish.
+struct OwnerRecord {
+    const uint32_t *p;
+    __device__ __forceinline__ unsigned long long key() const { return (unsigned long long)(0xffffffffu - p[0]); }
+    __device__ __forceinline__ void init(IndexEntry *e) const
+    {
+        e->first = key();
+        e->mask = (unsigned long long)p[1];
+    }
+    __device__ __forceinline__ void atomic(IndexEntry *e) const
+    {
+        atomicMax(&e->first, key());
+        atomicAdd(&e->mask, (unsigned long long)p[1]);
+    }
+    __device__ __forceinline__ void seq(IndexEntry *e) const
+    {
+        if (key() > e->first) e->first = key();
+        e->mask += p[1];
+    }
+};
 
 // oflags bit 3 = applied in claim
-// (claim rules as index.hip idx_claim_kernel: epoch-empty entries are claimed by CAS on the tag read,
-// the claimer initialises the batch-local fields with its own record, entries of earlier batches of
-// this epoch are applied at once, the rest deferred)
 template <int HW>
 __global__ void __launch_bounds__(256) own_claim_kernel(const uint32_t *__restrict__ x1, const int64_t *__restrict__ counts,
                                                         int64_t cap, IndexEntry *__restrict__ tab, int log2cap,
@@ -119,38 +133,9 @@ __global__ void __launch_bounds__(256) own_claim_kernel(const uint32_t *__restri
     uint32_t dw[HW];
 #pragma unroll
     for (int q = 0; q < HW; q++) dw[q] = rec[q];
-    const unsigned long long tag = tag_word(dw, key);
-    const uint64_t mask = (1ull << log2cap) - 1;
-    uint64_t h = tag_home(tag, log2cap);
-    bool mine = false;
-    for (uint64_t probe = 0;; probe++) {
-        if (probe > mask) { atomicOr(err, 2); return; }
-        IndexEntry *e = tab + h;
-        unsigned long long t = __hip_atomic_load(&e->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (!tag_live(t, key)) {
-            const unsigned long long old = atomicCAS(&e->tag, t, tag);
-            if (old == t) { mine = true; break; }
-            t = old;
-        }
-        if (mine) {
-            e->batch = cur;
-            e->first = (unsigned long long)(0xffffffffu - rec[HW]);    // this record (own_record)
-            e->mask = (unsigned long long)rec[HW + 1];
-            store_dig<HW>(e, dw);
-            break;
-        }
-        if (t == tag) break;
-        h = (h + 1) & mask;
-    }
-    oslot[r] = (uint32_t)h;
-    IndexEntry *e = tab + h;
-    bool apply = false;
-    if (!mine) {
-        const uint32_t bt = e->batch;
-        apply = bt >= bfirst && bt != cur && entry_matches<HW>(*e, dw);
-        if (apply) own_record(e, rec[HW], rec[HW + 1]);
-    }
-    oflags[r] = (mine || apply) ? 8 : 0;
+    bool applied;
+    if (!probe_claim<HW>(tab, log2cap, cur, bfirst, key, dw, OwnerRecord{rec + HW}, err, oslot + r, &applied)) return;
+    oflags[r] = applied ? 8 : 0;
 }
 
 template <int HW>
@@ -169,17 +154,10 @@ __global__ void __launch_bounds__(256) own_apply_kernel(const uint32_t *__restri
     uint32_t dw[HW];
 #pragma unroll
     for (int q = 0; q < HW; q++) dw[q] = rec[q];
-    IndexEntry *e = tab + oslot[r];
-    if (entry_matches<HW>(*e, dw)) {
-        own_record(e, rec[HW], rec[HW + 1]);
-    } else {
-        const uint32_t j = atomicAdd(ncoll, 1u);
-        if ((int)j < coll_cap) coll[j] = (uint32_t)r;
-        else atomicOr(err, 4);
-    }
+    probe_apply<HW>(tab + oslot[r], dw, OwnerRecord{rec + HW}, (uint32_t)r, coll, ncoll, coll_cap, err);
 }
 
-// exact sequential re-probe of 8-byte tag collisions (one thread)
+// exact sequential re-probe of the tag collisions (one thread)
 template <int HW>
 __global__ void own_slow_kernel(const uint32_t *__restrict__ x1, IndexEntry *__restrict__ tab, int log2cap, uint32_t cur,
                                 unsigned long long key, uint32_t *__restrict__ oslot,
@@ -188,30 +166,12 @@ __global__ void own_slow_kernel(const uint32_t *__restrict__ x1, IndexEntry *__r
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint32_t n = min(*ncoll, (uint32_t)coll_cap);
-    const uint64_t mask = (1ull << log2cap) - 1;
     for (uint32_t j = 0; j < n; j++) {
         const size_t r = coll[j];
         const uint32_t *rec = x1 + r * (HW + 2);
         uint32_t dw[HW];
         for (int q = 0; q < HW; q++) dw[q] = rec[q];
-        const unsigned long long tag = tag_word(dw, key);
-        uint64_t h = (oslot[r] + 1) & mask;
-        for (uint64_t probe = 0;; probe++) {
-            if (probe > mask) { *err |= 2; return; }
-            IndexEntry *e = tab + h;
-            if (!tag_live(e->tag, key)) {
-                e->tag = tag; e->batch = cur; e->mask = 0; e->first = 0;
-                store_dig<HW>(e, dw);
-                break;
-            }
-            if (e->tag == tag && entry_matches<HW>(*e, dw)) break;
-            h = (h + 1) & mask;
-        }
-        oslot[r] = (uint32_t)h;
-        IndexEntry *e = tab + h;
-        const unsigned long long key = 0xffffffffu - rec[HW];
-        if (key > e->first) e->first = key;
-        e->mask += rec[HW + 1];
+        if (!probe_slow<HW>(tab, log2cap, cur, key, dw, OwnerRecord{rec + HW}, oslot + r)) { *err |= 2; return; }
     }
 }
 
@@ -372,12 +332,10 @@ hipError_t launch_gx_emit(int hasher, const BlockState *bst, int nblocks, int ca
 {
     if (hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * G, st)) return e;
     dim3 g((ntiles + kEmitTiles - 1) / kEmitTiles, nblocks);
-    if (hasher == 0)
-        hipLaunchKernelGGL(gx_emit_kernel<5>, g, dim3(256), 0, st, bst, cap_blk, digests, scratch, slot, flags, gbase, G,
-                           x1, cap, counts, err);
-    else
-        hipLaunchKernelGGL(gx_emit_kernel<7>, g, dim3(256), 0, st, bst, cap_blk, digests, scratch, slot, flags, gbase, G,
-                           x1, cap, counts, err);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(gx_emit_kernel<decltype(hw)::value>, g, dim3(256), 0, st, bst, cap_blk, digests, scratch, slot,
+                           flags, gbase, G, x1, cap, counts, err);
+    });
     return hipGetLastError();
 }
 
@@ -386,25 +344,19 @@ hipError_t launch_gx_owner(int hasher, const uint32_t *x1, const int64_t *counts
                            uint8_t *oflags, uint32_t *coll, uint32_t *ncoll, int coll_cap, uint32_t *x2,
                            unsigned long long *x3exp, int *err, hipStream_t st)
 {
-    const int HW = hasher == 0 ? 5 : 7;
+    const int rw = (hasher == 0 ? 5 : 7) + 2;             // words of an X1 record
     dim3 g(gx_tiles(max_count), G);
     if (hipError_t e = hipMemsetAsync(ncoll, 0, sizeof(uint32_t), st)) return e;
-    if (hasher == 0) {
-        hipLaunchKernelGGL(own_claim_kernel<5>, g, dim3(256), 0, st, x1, counts, cap, tab, log2cap, cur, bfirst, tag_mask,
+    with_digest_words(hasher, [&](auto hw) {
+        constexpr int HW = decltype(hw)::value;
+        hipLaunchKernelGGL(own_claim_kernel<HW>, g, dim3(256), 0, st, x1, counts, cap, tab, log2cap, cur, bfirst, tag_mask,
                            oslot, oflags, err);
-        hipLaunchKernelGGL(own_apply_kernel<5>, g, dim3(256), 0, st, x1, counts, cap, tab, oslot, oflags, coll,
+        hipLaunchKernelGGL(own_apply_kernel<HW>, g, dim3(256), 0, st, x1, counts, cap, tab, oslot, oflags, coll, ncoll,
+                           coll_cap, err);
+        hipLaunchKernelGGL(own_slow_kernel<HW>, dim3(1), dim3(64), 0, st, x1, tab, log2cap, cur, tag_mask, oslot, coll,
                            ncoll, coll_cap, err);
-        hipLaunchKernelGGL(own_slow_kernel<5>, dim3(1), dim3(64), 0, st, x1, tab, log2cap, cur, tag_mask, oslot, coll,
-                           ncoll, coll_cap, err);
-    } else {
-        hipLaunchKernelGGL(own_claim_kernel<7>, g, dim3(256), 0, st, x1, counts, cap, tab, log2cap, cur, bfirst, tag_mask,
-                           oslot, oflags, err);
-        hipLaunchKernelGGL(own_apply_kernel<7>, g, dim3(256), 0, st, x1, counts, cap, tab, oslot, oflags, coll,
-                           ncoll, coll_cap, err);
-        hipLaunchKernelGGL(own_slow_kernel<7>, dim3(1), dim3(64), 0, st, x1, tab, log2cap, cur, tag_mask, oslot, coll,
-                           ncoll, coll_cap, err);
-    }
-    hipLaunchKernelGGL(own_decide_kernel, g, dim3(256), 0, st, x1, HW + 2, counts, cap, tab, oslot, cur, x2, x3exp, err);
+    });
+    hipLaunchKernelGGL(own_decide_kernel, g, dim3(256), 0, st, x1, rw, counts, cap, tab, oslot, cur, x2, x3exp, err);
     hipLaunchKernelGGL(own_finish_kernel, g, dim3(256), 0, st, x2, counts, cap, tab, err);
     return hipGetLastError();
 }

@@ -9,7 +9,8 @@
 //   * nCopy = (#distinct blocks holding the digest) mod 256; the location is the one SET by
 //     the first block's last occurrence (later SETs re-write the decoded location).
 //
-// Batched formulation (blocks b = 0..63 of a batch, in arrival order):
+// Batched formulation (blocks b = 0..63 of a batch, in arrival order); claim / apply / slow are the
+// table's probe protocol (index_probe.hpp) with a chunk's occurrence as the record:
 //   claim  — probe open addressing by the 8-byte tag; CAS-claim empty slots
 //   apply  — verify the full digest; atomicOr(mask, 1<<b); atomicMax(first, (63-b)<<32|k)
 //   slow   — single-thread exact re-probe for the (astronomically rare) 8-byte tag collisions
@@ -17,29 +18,40 @@
 //            last chunk index) is the one chunk that writes the final value (in store.hip)
 #include <cstdlib>
 
+#include "index_probe.hpp"
 #include "launchers.hpp"
 
 namespace hdrf {
 
-// Block b holds the digest: set its batch-mask bit.  Only a REPEAT inside one block (the bit was
-// already set) records its key in `first` = max((63-b)<<32 | k+1); decide completes the max over
-// the minimum block's occurrences when that block has repeats.  One returning atomic per chunk.
-__device__ __forceinline__ void record_occurrence(IndexEntry *e, int b, int k)
-{
-    const unsigned long long bit = 1ull << b;
-    const unsigned long long old = atomicOr(&e->mask, bit);
-    if (old & bit) atomicMax(&e->first, ((unsigned long long)(63 - b) << 32) | (unsigned)(k + 1));
-}
+// The record policy (index_probe.hpp) of a chunk: occurrence k of block b.  Block b holds the digest:
+// set its batch-mask bit.  Only a REPEAT inside one block (the bit was already set) records its key
+// in `first` = max((63-b)<<32 | k+1); decide completes the max over the minimum block's occurrences
+// when that block has repeats.  One returning atomic per chunk.
+struct BlockOccurrence {
+    int b, k;
+    __device__ __forceinline__ unsigned long long bit() const { return 1ull << b; }
+    __device__ __forceinline__ unsigned long long key() const
+    {
+        return ((unsigned long long)(63 - b) << 32) | (unsigned)(k + 1);
+    }
+    __device__ __forceinline__ void init(IndexEntry *e) const
+    {
+        e->mask = bit();
+        e->first = 0;
+    }
+    __device__ __forceinline__ void atomic(IndexEntry *e) const
+    {
+        const unsigned long long old = atomicOr(&e->mask, bit());
+        if (old & bit()) atomicMax(&e->first, key());
+    }
+    __device__ __forceinline__ void seq(IndexEntry *e) const
+    {
+        if ((e->mask & bit()) && key() > e->first) e->first = key();
+        e->mask |= bit();
+    }
+};
 
-// ---- claim: grid (ceil(cap_blk/256), nblocks) ---------------------------------------------
-// Probe by tag; CAS-claim empty slots (an entry of an older epoch is empty: the CAS replaces the
-// tag it read).  The chunk's block bit / last occurrence are applied right here when the digest is
-// known to match: the claimer (its digest IS the entry's: it initialises the batch-local fields
-// with its own occurrence), or an entry created by an earlier batch of this epoch (batch in
-// [bfirst, cur): its digest bytes are immutable).  Tag hits on entries created in this batch by
-// another lane are deferred to apply (their digest bytes may not be visible yet) — and so is a
-// stale `batch` of the previous epoch read between another lane's CAS and its batch store (such
-// ids are < bfirst).  flags bit 3 = applied.
+// ---- claim: grid (ceil(cap_blk/256), nblocks); flags bit 3 = applied -------------------------
 template <int HW>
 __global__ void __launch_bounds__(256) idx_claim_kernel(const BlockState *__restrict__ bst, int cap_blk,
                                                         const uint32_t *__restrict__ digests,
@@ -55,38 +67,9 @@ __global__ void __launch_bounds__(256) idx_claim_kernel(const BlockState *__rest
     uint32_t dw[HW];
 #pragma unroll
     for (int i = 0; i < HW; i++) dw[i] = digests[c * HW + i];
-    const unsigned long long tag = tag_word(dw, key);
-    const uint64_t mask = (1ull << log2cap) - 1;
-    uint64_t h = tag_home(tag, log2cap);
-    bool mine = false;
-    for (uint64_t probe = 0;; probe++) {
-        if (probe > mask) { atomicOr(err, 2); return; }           // table full
-        IndexEntry *e = tab + h;
-        unsigned long long t = __hip_atomic_load(&e->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (!tag_live(t, key)) {                                // empty: claim it
-            const unsigned long long old = atomicCAS(&e->tag, t, tag);
-            if (old == t) { mine = true; break; }
-            t = old;
-        }
-        if (mine) {
-            e->batch = cur;
-            e->mask = 1ull << b;                                   // this chunk's occurrence
-            e->first = 0;
-            store_dig<HW>(e, dw);
-            break;
-        }
-        if (t == tag) break;
-        h = (h + 1) & mask;
-    }
-    slot[c] = (uint32_t)h;
-    IndexEntry *e = tab + h;
-    bool apply = false;
-    if (!mine) {
-        const uint32_t bt = e->batch;
-        apply = bt >= bfirst && bt != cur && entry_matches<HW>(*e, dw);
-        if (apply) record_occurrence(e, b, k);
-    }
-    flags[c] = (mine || apply) ? 8 : 0;
+    bool applied;
+    if (!probe_claim<HW>(tab, log2cap, cur, bfirst, key, dw, BlockOccurrence{b, k}, err, slot + c, &applied)) return;
+    flags[c] = applied ? 8 : 0;
 }
 
 // ---- apply: deferred chunks — verify full digest, record block membership / last occurrence
@@ -106,14 +89,7 @@ __global__ void __launch_bounds__(256) idx_apply_kernel(const BlockState *__rest
     uint32_t dw[HW];
 #pragma unroll
     for (int i = 0; i < HW; i++) dw[i] = digests[c * HW + i];
-    IndexEntry *e = tab + slot[c];
-    if (entry_matches<HW>(*e, dw)) {
-        record_occurrence(e, b, k);
-    } else {
-        uint32_t i = atomicAdd(ncoll, 1u);
-        if ((int)i < coll_cap) coll[i] = (uint32_t)c;
-        else atomicOr(err, 4);
-    }
+    probe_apply<HW>(tab + slot[c], dw, BlockOccurrence{b, k}, (uint32_t)c, coll, ncoll, coll_cap, err);
 }
 
 // ---- slow path: one thread, exact sequential re-probe of tag-collided chunks --------------
@@ -125,33 +101,12 @@ __global__ void idx_slow_kernel(int cap_blk, const uint32_t *__restrict__ digest
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint32_t n = min(*ncoll, (uint32_t)coll_cap);
-    const uint64_t mask = (1ull << log2cap) - 1;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t c = coll[i];
         const int b = (int)(c / (uint32_t)cap_blk), k = (int)(c % (uint32_t)cap_blk);
         uint32_t dw[HW];
         for (int q = 0; q < HW; q++) dw[q] = digests[(size_t)c * HW + q];
-        const unsigned long long tag = tag_word(dw, key);
-        uint64_t h = (slot[c] + 1) & mask;
-        for (uint64_t probe = 0;; probe++) {
-            if (probe > mask) { *err |= 2; return; }
-            IndexEntry *e = tab + h;
-            if (!tag_live(e->tag, key)) {
-                e->tag = tag; e->batch = cur; e->mask = 0; e->first = 0;
-                store_dig<HW>(e, dw);
-                break;
-            }
-            if (e->tag == tag && entry_matches<HW>(*e, dw)) break;
-            h = (h + 1) & mask;
-        }
-        slot[c] = (uint32_t)h;
-        IndexEntry *e = tab + h;
-        const unsigned long long bit = 1ull << b;
-        if (e->mask & bit) {
-            const unsigned long long f = ((unsigned long long)(63 - b) << 32) | (unsigned)(k + 1);
-            if (f > e->first) e->first = f;
-        }
-        e->mask |= bit;
+        if (!probe_slow<HW>(tab, log2cap, cur, key, dw, BlockOccurrence{b, k}, slot + c)) { *err |= 2; return; }
     }
 }
 
@@ -285,33 +240,20 @@ __global__ void __launch_bounds__(256) idx_load_kernel(const uint32_t *__restric
     uint32_t dw[HW];
 #pragma unroll
     for (int i = 0; i < HW; i++) dw[i] = dw_all[(size_t)k * HW + i];
-    const unsigned long long tag = tag_word(dw, key);
-    const uint64_t mask = (1ull << log2cap) - 1;
-    uint64_t h = tag_home(tag, log2cap);
-    for (uint64_t probe = 0; probe <= mask; probe++, h = (h + 1) & mask) {
-        unsigned long long t = tab[h].tag;
-        bool mine = false;
-        while (!tag_live(t, key)) {
-            const unsigned long long old = atomicCAS(&tab[h].tag, t, tag);
-            if (old == t) { mine = true; break; }
-            t = old;
-        }
-        if (!mine) continue;
-        IndexEntry &e = tab[h];
-        const uint8_t *v = vals + (size_t)k * 11;           // chunkMeta.process, DN/chunkMeta.java:35-60
-        e.mask = 0;
-        e.first = 0;
-        e.batch = bload;                                    // a batch before every batch that follows
-        e.ncopy = v[0] | (HW == 7 ? (dw[1] >> 24) << 8 : 0u);
-        e.cid = ((uint32_t)v[1] << 16) | ((uint32_t)v[2] << 8) | v[3];
-        e.start = ((uint32_t)v[4] << 16) | ((uint32_t)v[5] << 8) | v[6] | ((uint32_t)(v[10] & 0xF0) << 20);
-        e.stop = ((uint32_t)v[7] << 16) | ((uint32_t)v[8] << 8) | v[9] | ((uint32_t)(v[10] & 0x0F) << 24);
+    IndexEntry *ep = probe_claim_empty(tab, log2cap, key, tag_word(dw, key));
+    if (!ep) { atomicOr(err, 2); return; }                  // table full
+    IndexEntry &e = *ep;
+    const uint8_t *v = vals + (size_t)k * 11;               // chunkMeta.process, DN/chunkMeta.java:35-60
+    e.mask = 0;
+    e.first = 0;
+    e.batch = bload;                                        // a batch before every batch that follows
+    e.ncopy = v[0] | (HW == 7 ? (dw[1] >> 24) << 8 : 0u);
+    e.cid = ((uint32_t)v[1] << 16) | ((uint32_t)v[2] << 8) | v[3];
+    e.start = ((uint32_t)v[4] << 16) | ((uint32_t)v[5] << 8) | v[6] | ((uint32_t)(v[10] & 0xF0) << 20);
+    e.stop = ((uint32_t)v[7] << 16) | ((uint32_t)v[8] << 8) | v[9] | ((uint32_t)(v[10] & 0x0F) << 24);
 #pragma unroll
-        for (int i = 2; i < HW; i++) e.dig[i - 2] = dw[i];
-        if (HW == 5) { e.dig[3] = dw[0]; e.dig[4] = dw[1]; }
-        return;
-    }
-    atomicOr(err, 2);                                       // table full
+    for (int i = 2; i < HW; i++) e.dig[i - 2] = dw[i];
+    if (HW == 5) { e.dig[3] = dw[0]; e.dig[4] = dw[1]; }
 }
 
 hipError_t launch_index_load(int hasher, const uint32_t *dw, const uint8_t *vals, int n, IndexEntry *tab, int log2cap,
@@ -319,10 +261,10 @@ hipError_t launch_index_load(int hasher, const uint32_t *dw, const uint8_t *vals
 {
     if (n <= 0) return hipSuccess;
     const dim3 g((n + 255) / 256);
-    if (hasher == 0)
-        hipLaunchKernelGGL(idx_load_kernel<5>, g, dim3(256), 0, st, dw, vals, n, tab, log2cap, key, bload, err);
-    else
-        hipLaunchKernelGGL(idx_load_kernel<7>, g, dim3(256), 0, st, dw, vals, n, tab, log2cap, key, bload, err);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(idx_load_kernel<decltype(hw)::value>, g, dim3(256), 0, st, dw, vals, n, tab, log2cap, key, bload,
+                           err);
+    });
     return hipGetLastError();
 }
 
@@ -365,8 +307,10 @@ hipError_t launch_index_probe(int hasher, const BlockState *bst, int nblocks, in
                               unsigned long long *stats, hipStream_t st)
 {
     dim3 g((cap_blk + 255) / 256, nblocks);
-    if (hasher == 0) hipLaunchKernelGGL(idx_probe_kernel<5>, g, dim3(256), 0, st, bst, cap_blk, digests, slot, log2cap, tag_mask, stats);
-    else hipLaunchKernelGGL(idx_probe_kernel<7>, g, dim3(256), 0, st, bst, cap_blk, digests, slot, log2cap, tag_mask, stats);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(idx_probe_kernel<decltype(hw)::value>, g, dim3(256), 0, st, bst, cap_blk, digests, slot, log2cap,
+                           tag_mask, stats);
+    });
     return hipGetLastError();
 }
 
@@ -392,27 +336,17 @@ hipError_t launch_index(int hasher, const BlockState *bst, int nblocks, int cap_
     dim3 g(ntiles, nblocks);
     static const int lds = env_int("HDRF_CLAIM_LDS", 0);
     if (hipError_t e = hipMemsetAsync(ncoll, 0, sizeof(uint32_t), st)) return e;
-    if (hasher == 0) {
-        hipLaunchKernelGGL(idx_claim_kernel<5>, g, dim3(256), lds, st, bst, cap_blk, digests, tab, log2cap, cur, bfirst,
+    with_digest_words(hasher, [&](auto hw) {
+        constexpr int HW = decltype(hw)::value;
+        hipLaunchKernelGGL(idx_claim_kernel<HW>, g, dim3(256), lds, st, bst, cap_blk, digests, tab, log2cap, cur, bfirst,
                            tag_mask, slot, flags, err);
         mk->mark(st);
-        hipLaunchKernelGGL(idx_apply_kernel<5>, g, dim3(256), 0, st, bst, cap_blk, digests, tab, slot, flags, coll,
-                           ncoll,
+        hipLaunchKernelGGL(idx_apply_kernel<HW>, g, dim3(256), 0, st, bst, cap_blk, digests, tab, slot, flags, coll, ncoll,
                            coll_cap, err);
         mk->mark(st);
-        hipLaunchKernelGGL(idx_slow_kernel<5>, dim3(1), dim3(64), 0, st, cap_blk, digests, tab, log2cap, cur, tag_mask, slot,
-                           coll, ncoll, coll_cap, err);
-    } else {
-        hipLaunchKernelGGL(idx_claim_kernel<7>, g, dim3(256), lds, st, bst, cap_blk, digests, tab, log2cap, cur, bfirst,
-                           tag_mask, slot, flags, err);
-        mk->mark(st);
-        hipLaunchKernelGGL(idx_apply_kernel<7>, g, dim3(256), 0, st, bst, cap_blk, digests, tab, slot, flags, coll,
-                           ncoll,
-                           coll_cap, err);
-        mk->mark(st);
-        hipLaunchKernelGGL(idx_slow_kernel<7>, dim3(1), dim3(64), 0, st, cap_blk, digests, tab, log2cap, cur, tag_mask, slot,
-                           coll, ncoll, coll_cap, err);
-    }
+        hipLaunchKernelGGL(idx_slow_kernel<HW>, dim3(1), dim3(64), 0, st, cap_blk, digests, tab, log2cap, cur, tag_mask,
+                           slot, coll, ncoll, coll_cap, err);
+    });
     hipLaunchKernelGGL(idx_decide_kernel, g, dim3(256), 0, st, bst, cap_blk, offsets, tab, slot, cur, flags, tilesum,
                        ntiles, dcnt);
     return hipGetLastError();

@@ -286,12 +286,10 @@ hipError_t launch_lane_hash(int hasher, const BlockDesc *d_blocks, int nblocks, 
                             uint32_t *sdig, uint32_t *bdig, int *gm_need, int *err, hipStream_t st)
 {
     const dim3 g((total_waves + 3) / 4);
-    if (hasher == 0)
-        hipLaunchKernelGGL(lane_hash_kernel<5>, g, dim3(256), 0, st, d_blocks, nblocks, total_waves, w, maxlen, spec, cap,
-                           meta, rq, rq_count, rq_cap, irr, sdig, bdig, gm_need, err);
-    else
-        hipLaunchKernelGGL(lane_hash_kernel<7>, g, dim3(256), 0, st, d_blocks, nblocks, total_waves, w, maxlen, spec, cap,
-                           meta, rq, rq_count, rq_cap, irr, sdig, bdig, gm_need, err);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(lane_hash_kernel<decltype(hw)::value>, g, dim3(256), 0, st, d_blocks, nblocks, total_waves, w, maxlen,
+                           spec, cap, meta, rq, rq_count, rq_cap, irr, sdig, bdig, gm_need, err);
+    });
     return hipGetLastError();
 }
 

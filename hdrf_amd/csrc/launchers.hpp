@@ -1,6 +1,7 @@
 // launchers.hpp — host-side kernel launchers shared by the api*.hip files (one stream per context).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -13,6 +14,15 @@ __attribute__((visibility("hidden"))) inline int env_int(const char *name, int d
 {
     const char *e = std::getenv(name);
     return e ? std::atoi(e) : dflt;
+}
+
+// The digest width of a hasher (0 SHA-1: 5 words, 1 SHA-224: 7) as a compile-time constant: calls
+// f(std::integral_constant<int, HW>), so a launcher spells the launches of its kernel templates once.
+template <class F>
+__attribute__((visibility("hidden"))) inline void with_digest_words(int hasher, F &&f)
+{
+    if (hasher == 0) f(std::integral_constant<int, 5>{});
+    else f(std::integral_constant<int, 7>{});
 }
 
 // Stage markers: when timing is on, a HIP event is recorded on the launch stream at every

@@ -7,13 +7,14 @@
 // DN/chunkMeta.java:35-60), and threadedConstructor copies container[start, stop) to
 // data[bbStart, bbStop) (:474-531).
 //
-//   rd_lookup — one lane per chunk: probe the index (same open addressing as index.hip), decode
+//   rd_lookup — one lane per chunk: probe the index (index_probe.hpp probe_find), decode
 //               (container id, start, stop), and the readable copy of the container (an arena
 //               slot, or a container loaded back from its file with hdrf_container_load)
 //   rd_scan   — one workgroup: exclusive prefix of the chunk lengths (block offsets) + total
 //   rd_gather — one wave per chunk: 16-B-per-lane copy arena -> output block
 //   gx_locate — node-global contexts: the owner's lookup of the digests it owns (location +
 //               placing rank); each rank then gathers the chunks it placed (hdrf_gx_read_*)
+#include "index_probe.hpp"
 #include "launchers.hpp"
 
 namespace hdrf {
@@ -23,23 +24,6 @@ struct RdChunk {
     uint32_t start, len;
     uint32_t off;        // offset in the rebuilt block
 };
-
-// probe the index for one digest (the open addressing of index.hip); nullptr when absent
-template <int HW>
-__device__ const IndexEntry *rd_probe(const uint32_t *dw, const IndexEntry *__restrict__ tab, int log2cap,
-                                      unsigned long long key)
-{
-    const unsigned long long tag = tag_word(dw, key);
-    const uint64_t mask = (1ull << log2cap) - 1;
-    uint64_t h = tag_home(tag, log2cap);
-    for (uint64_t probe = 0; probe <= mask; probe++) {
-        const IndexEntry &e = tab[h];
-        if (!tag_live(e.tag, key)) return nullptr;           // empty (or of an older epoch)
-        if (e.tag == tag && entry_matches<HW>(e, dw)) return &e;
-        h = (h + 1) & mask;
-    }
-    return nullptr;
-}
 
 template <int HW>
 __global__ void __launch_bounds__(256) rd_lookup_kernel(const uint32_t *__restrict__ dig, int n,
@@ -54,7 +38,7 @@ __global__ void __launch_bounds__(256) rd_lookup_kernel(const uint32_t *__restri
     for (int i = 0; i < HW; i++) dw[i] = dig[(size_t)k * HW + i];
     RdChunk r;
     r.slot = 0xffffffffu; r.start = 0; r.len = 0; r.off = 0;
-    const IndexEntry *e = rd_probe<HW>(dw, tab, log2cap, tag_mask);
+    const IndexEntry *e = probe_find<HW>(dw, tab, log2cap, tag_mask);
     if (e) {
         r.start = e->start;
         r.len = e->stop - e->start;                    // chunkMeta.length = blockStop - blockStart
@@ -86,7 +70,7 @@ __global__ void __launch_bounds__(256) gx_locate_kernel(const uint32_t *__restri
     for (int i = 0; i < HW; i++) dw[i] = dig[(size_t)k * HW + i];
     uint4 v = make_uint4(0, 0, 0, 0);
     if ((int)(dw[0] % (uint32_t)G) == rank) {
-        const IndexEntry *e = rd_probe<HW>(dw, tab, log2cap, tag_mask);
+        const IndexEntry *e = probe_find<HW>(dw, tab, log2cap, tag_mask);
         if (e) v = make_uint4(e->cid & 0xffffffu, e->start, e->stop, e->cid >> 24);
         if (!e || v.w == 0u) atomicOr(err, 1);        // missing, or a location without its placer
     }
@@ -154,12 +138,10 @@ hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const Inde
     if (n <= 0) return hipSuccess;
     if (!gather) {
         const dim3 g((n + 255) / 256);
-        if (hasher == 0)
-            hipLaunchKernelGGL(rd_lookup_kernel<5>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask, cids, ncont, c,
-                               err);
-        else
-            hipLaunchKernelGGL(rd_lookup_kernel<7>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask, cids, ncont, c,
-                               err);
+        with_digest_words(hasher, [&](auto hw) {
+            hipLaunchKernelGGL(rd_lookup_kernel<decltype(hw)::value>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask,
+                               cids, ncont, c, err);
+        });
         hipLaunchKernelGGL(rd_scan_kernel, dim3(1), dim3(1024), 0, st, c, n, total);
     } else {
         hipLaunchKernelGGL(rd_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, st, c, n, bases, out);
@@ -174,10 +156,10 @@ hipError_t launch_gx_locate(int hasher, const uint32_t *dig, int n, const IndexE
 {
     if (n <= 0) return hipSuccess;
     const dim3 g((n + 255) / 256);
-    if (hasher == 0)
-        hipLaunchKernelGGL(gx_locate_kernel<5>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask, G, rank, loc, err);
-    else
-        hipLaunchKernelGGL(gx_locate_kernel<7>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask, G, rank, loc, err);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(gx_locate_kernel<decltype(hw)::value>, g, dim3(256), 0, st, dig, n, tab, log2cap, tag_mask, G,
+                           rank, loc, err);
+    });
     return hipGetLastError();
 }
 

@@ -320,10 +320,10 @@ hipError_t launch_sha_need(int hasher, const BlockDesc *d_blocks, int nblocks, c
     mk->mark(st);
     const int tiles = (cap_blk + 1023) / 1024;
     hipLaunchKernelGGL(need_list_kernel, dim3(tiles, nblocks), dim3(256), 0, st, bst, cap_blk, need, list, queue + 66);
-    if (hasher == 0)
-        hipLaunchKernelGGL(sha_list_kernel<5>, dim3(64), dim3(256), 0, st, d_blocks, offsets, cap_blk, digests, list, queue + 66);
-    else
-        hipLaunchKernelGGL(sha_list_kernel<7>, dim3(64), dim3(256), 0, st, d_blocks, offsets, cap_blk, digests, list, queue + 66);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(sha_list_kernel<decltype(hw)::value>, dim3(64), dim3(256), 0, st, d_blocks, offsets, cap_blk,
+                           digests, list, queue + 66);
+    });
     mk->mark(st);
     return hipGetLastError();
 }
@@ -360,14 +360,17 @@ hipError_t launch_sha(int hasher, const BlockDesc *d_blocks, int nblocks, const 
     static const bool carryk = env_int("HDRF_SHA_CARRY", 1) != 0;
     const int wpb = std::max(4, (per_cu * 256 / nblocks) & ~3);
     dim3 g(wpb / 4, nblocks + 1);                  // y = 0: the long-chunk lanes
-    if (carryk && hasher == 0)
-        hipLaunchKernelGGL(sha_carry_kernel<5>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk, digests, queue, thr, (setprio_mask() >> 2) & 3);
-    else if (carryk)
-        hipLaunchKernelGGL(sha_carry_kernel<7>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk, digests, queue, thr, (setprio_mask() >> 2) & 3);
-    else if (hasher == 0)
-        hipLaunchKernelGGL(sha_chunk_kernel<5>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk, digests, queue, thr, (setprio_mask() >> 2) & 3);
+    const int prio = (setprio_mask() >> 2) & 3;
+    if (carryk)
+        with_digest_words(hasher, [&](auto hw) {
+            hipLaunchKernelGGL(sha_carry_kernel<decltype(hw)::value>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk,
+                               digests, queue, thr, prio);
+        });
     else
-        hipLaunchKernelGGL(sha_chunk_kernel<7>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk, digests, queue, thr, (setprio_mask() >> 2) & 3);
+        with_digest_words(hasher, [&](auto hw) {
+            hipLaunchKernelGGL(sha_chunk_kernel<decltype(hw)::value>, g, dim3(256), lds, st, d_blocks, offsets, bst, cap_blk,
+                               digests, queue, thr, prio);
+        });
     mk->mark(st);                                  // (the stage timer's former tail slot: empty)
     return hipGetLastError();
 }

@@ -294,12 +294,10 @@ hipError_t launch_vf_hash_items(int hasher, const void *items, const IndexEntry 
                                 hipStream_t st)
 {
     const dim3 g(std::max(1, wgs));
-    if (hasher == 0)
-        hipLaunchKernelGGL((vf_hash_kernel<5, false>), g, dim3(256), 0, st, (const VfItem *)items, nullptr, 0u, nullptr, tab,
-                           slot0, bases, allocs, nullptr, 0u, 0ull, bad, C);
-    else
-        hipLaunchKernelGGL((vf_hash_kernel<7, false>), g, dim3(256), 0, st, (const VfItem *)items, nullptr, 0u, nullptr, tab,
-                           slot0, bases, allocs, nullptr, 0u, 0ull, bad, C);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, false>), g, dim3(256), 0, st, (const VfItem *)items, nullptr,
+                           0u, nullptr, tab, slot0, bases, allocs, nullptr, 0u, 0ull, bad, C);
+    });
     return hipGetLastError();
 }
 
@@ -311,12 +309,10 @@ hipError_t launch_vf_hash_block(int hasher, const void *chunks, int n, const uin
     // load_win fetches dwords at base + (pos & ~3): the base goes down to a dword, the rest into pos
     const uint32_t mis = (uint32_t)((uintptr_t)block & 3u);
     const dim3 g(std::max(1, std::min(wgs, (n + 255) / 256)));
-    if (hasher == 0)
-        hipLaunchKernelGGL((vf_hash_kernel<5, true>), g, dim3(256), 0, st, nullptr, (const RdChunkV *)chunks, (uint32_t)n, dig,
-                           nullptr, 0ull, nullptr, nullptr, block - mis, mis, block_bytes + mis, nullptr, C);
-    else
-        hipLaunchKernelGGL((vf_hash_kernel<7, true>), g, dim3(256), 0, st, nullptr, (const RdChunkV *)chunks, (uint32_t)n, dig,
-                           nullptr, 0ull, nullptr, nullptr, block - mis, mis, block_bytes + mis, nullptr, C);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, true>), g, dim3(256), 0, st, nullptr, (const RdChunkV *)chunks,
+                           (uint32_t)n, dig, nullptr, 0ull, nullptr, nullptr, block - mis, mis, block_bytes + mis, nullptr, C);
+    });
     return hipGetLastError();
 }
 
@@ -325,8 +321,9 @@ hipError_t launch_vf_rows(int hasher, const uint32_t *bad, uint32_t from, uint32
 {
     if (n == 0) return hipSuccess;
     const dim3 g((n + 255) / 256);
-    if (hasher == 0) hipLaunchKernelGGL(vf_rows_kernel<5>, g, dim3(256), 0, st, bad, from, n, tab, slot0, out);
-    else hipLaunchKernelGGL(vf_rows_kernel<7>, g, dim3(256), 0, st, bad, from, n, tab, slot0, out);
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL(vf_rows_kernel<decltype(hw)::value>, g, dim3(256), 0, st, bad, from, n, tab, slot0, out);
+    });
     return hipGetLastError();
 }
 

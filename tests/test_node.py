@@ -20,14 +20,9 @@ from node_harness import mixed_blocks as _mixed_blocks, plan as _plan
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("G,hasher,sched", [
-    (2, 0, [[2, 3], [3, 1], [1, 1]]),
-    (3, 1, [[2, 2, 2], [1, 3, 2]]),
-    (4, 0, [[1, 2, 1, 2], [2, 1, 1, 1]]),
-    (8, 0, [[1, 2, 1, 1, 2, 1, 1, 1], [2, 1, 1, 2, 1, 1, 2, 1]]),    # the node's rank count
-])
-def test_node_loopback_matches_single_sequence(G, hasher, sched):
+def _loopback_vs_oracle(G, hasher, sched, **extra_cfg):
+    """G loopback ranks over the schedule against one oracle: boundaries, digests, decisions, index
+    values, allocator, recipes, container bytes and the node read.  Returns the oracle's index keys."""
     import torch  # noqa: F401
     from node_harness import Loopback, assemble_containers, loopback_read, merged_index, open_ranks
     from oracle.oracle import Oracle
@@ -36,7 +31,7 @@ def test_node_loopback_matches_single_sequence(G, hasher, sched):
     seq = _plan(sched)
     blocks = _mixed_blocks(7 + G, len(seq), 700_000)
     ctxs = open_ranks(G, hasher=hasher, container_max=cmax, max_block_bytes=4 << 20, max_batch_blocks=4,
-                      index_log2=20, arena_slots=256)
+                      index_log2=20, arena_slots=256, **extra_cfg)
     lb = Loopback(ctxs)
     ora = Oracle(hasher=hasher, compressor=1, max_size=cmax)
     devs = []
@@ -98,6 +93,43 @@ def test_node_loopback_matches_single_sequence(G, hasher, sched):
         c.dev_free(p)
     for c in ctxs:
         c.close()
+    return ok
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G,hasher,sched", [
+    (2, 0, [[2, 3], [3, 1], [1, 1]]),
+    (3, 1, [[2, 2, 2], [1, 3, 2]]),
+    (4, 0, [[1, 2, 1, 2], [2, 1, 1, 1]]),
+    (8, 0, [[1, 2, 1, 1, 2, 1, 1, 1], [2, 1, 1, 2, 1, 1, 2, 1]]),    # the node's rank count
+])
+def test_node_loopback_matches_single_sequence(G, hasher, sched):
+    _loopback_vs_oracle(G, hasher, sched)
+
+
+def _tag_collisions_per_owner(keys, G, bits):
+    """Digests per owner rank that share their truncated index tag with an earlier digest of that
+    owner.  The rules of the kernels: the digest words are the digest bytes read little-endian,
+    owner = first word mod G (gx.hip owner_of), tag = the low `bits` bits of the first two words
+    (common.hpp tag_word under debug_tag_bits)."""
+    w = np.ascontiguousarray(keys[:, :8]).view("<u4").astype(np.uint64)
+    owner = w[:, 0] % np.uint64(G)
+    tag = (w[:, 0] | (w[:, 1] << np.uint64(32))) & np.uint64((1 << bits) - 1)
+    return [int((owner == r).sum()) - int(np.unique(tag[owner == r]).size) for r in range(G)]
+
+
+@pytest.mark.gpu
+def test_node_loopback_tag_collisions():
+    """The owner side under forced tag collisions (debug_tag_bits = 16): distinct digests of one
+    owner that share a tag take the mismatch branch of own_apply_kernel and the exact re-probe of
+    own_slow_kernel (and the scratch table of the front takes idx_apply / idx_slow), and the node
+    still equals the oracle, which keys on whole digests.  At least 16 colliding digests per owner,
+    counted on the CPU from the oracle's keys, so the test cannot pass without collisions."""
+    G, bits = 2, 16
+    keys = _loopback_vs_oracle(G, 0, [[2, 3], [3, 1], [1, 1]], debug_tag_bits=bits)
+    coll = _tag_collisions_per_owner(keys, G, bits)
+    print("distinct digests", len(keys), "tag collisions per owner", coll)
+    assert min(coll) >= 16, f"too few tag collisions per owner: {coll}"
 
 
 @pytest.mark.gpu
