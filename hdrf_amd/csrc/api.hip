@@ -67,7 +67,7 @@ static void free_slot(Slot &S)
     void *dev[] = {S.d_blocks, S.d_spec, S.d_meta, S.d_gm, S.d_irr, S.d_path, S.d_jx, S.d_jt, S.d_wgsum, S.d_rq, S.d_rq_count, S.d_rqkeep, S.d_bst, S.d_off, S.d_dig, S.d_slot,
                    S.d_pre, S.d_flags, S.d_dcnt, S.d_tilesum, S.d_tilepre, S.d_store, S.d_rstate, S.d_ev, S.d_closed,
                    S.d_nclosed, S.d_coll, S.d_ncoll, S.d_pcid, S.d_ppos, S.d_queue, S.d_segclen, S.d_filelen, S.d_err,
-                   S.d_lzwork, S.d_sdig, S.d_bdig, S.d_need, S.d_nlist, S.d_gmneed};
+                   S.d_lzwork};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {S.h_bst, S.h_store, S.h_alloc, S.h_err, S.h_nclosed, S.h_long, S.h_closed, S.h_filelen, S.h_desc,
@@ -196,7 +196,6 @@ static int alloc_slot(hdrf_ctx *ctx, Slot &S)
 }
 
 static int wait_one(hdrf_ctx *ctx, bool force = false);
-static bool fused_front();
 static int init_state(hdrf_ctx *ctx, bool fresh);
 static bool gen_undrained(const hdrf_ctx *ctx);
 
@@ -410,7 +409,6 @@ extern "C" int hdrf_open(const hdrf_cfg *cfg_in, hdrf_ctx **out)
             rc = set_err(ctx, HDRF_E_HIP, "hipMemset failed");
     }
     ctx->timing = c.timing != 0;
-    ctx->fused = fused_front() && c.n_ranks <= 1;     // (node-global fronts keep the two-pass front)
     {
         int ncu = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device) == hipSuccess && ncu > 0)
@@ -515,14 +513,6 @@ ChunkScratch host::chunk_scratch(Slot &S, int compressor)
     return X;
 }
 
-// HDRF_FUSED=1: the front cuts and hashes in one pass over the bytes (lanehash.hip) instead of the
-// granule pass + lane walk (chunk.hip) followed by the SHA lanes (sha.hip); single-node contexts.
-// Read when a context opens, so a process may hold contexts of both kinds (the tests do).
-static bool fused_front()
-{
-    return env_int("HDRF_FUSED", 0) != 0;
-}
-
 // Validate a batch and fill the slot's (pinned) descriptors: the lane segmentation of the chunking
 // pass (chunk.hip).  seg_len = segment_bytes / 63 rounded down to a multiple of window + 2, within
 // [4, 20] x 702 B.  Grows the slot's speculative lists when needed (the slot's previous batch has
@@ -533,12 +523,11 @@ int host::prepare_blocks(hdrf_ctx *ctx, Slot &S, int32_t nblocks, const uint8_t 
     if (nblocks < 1 || nblocks > ctx->max_batch || !dev_data || !len || !readable)
         return set_err(ctx, HDRF_E_INVAL, "bad batch arguments");
     const hdrf_cfg &c = ctx->cfg;
-    int64_t total = 0, max_len = 0;
+    int64_t max_len = 0;
     for (int b = 0; b < nblocks; b++) {
         if ((int64_t)len[b] > c.max_block_bytes) return set_err(ctx, HDRF_E_INVAL, "block larger than max_block_bytes");
         if (readable[b] < len[b] + kSlack) return set_err(ctx, HDRF_E_INVAL, "readable must be >= len + 64");
         if (((uintptr_t)dev_data[b] & 15) != 0) return set_err(ctx, HDRF_E_INVAL, "block data must be 16-B aligned");
-        total += (int64_t)len[b];
         max_len = std::max(max_len, (int64_t)len[b]);
     }
     S.max_len = max_len;
@@ -547,26 +536,9 @@ int host::prepare_blocks(hdrf_ctx *ctx, Slot &S, int32_t nblocks, const uint8_t 
     // follows segment_bytes alone (shorter segments only raise the share of boundaries whose
     // chains have not met within the next segment, which then take the repair pass)
     int wins = std::max(kSegMinWin, std::min(kSegMaxWin, (int)(c.segment_bytes / kWaveSegs / unit)));
-    // HDRF_SEG_WINS (A/B): the two-pass front's segment length in windows, over segment_bytes
+    // HDRF_SEG_WINS (A/B): the segment length in windows, over segment_bytes
     static const int wins_env = env_int("HDRF_SEG_WINS", 0);
-    if (wins_env > 0 && !ctx->fused) wins = std::max(kSegMinWin, std::min(kSegMaxWin, wins_env));
-    if (ctx->fused) {
-        // the fused pass (lanehash.hip): every lane does the same work (its segment, 64 B per step),
-        // so a second, partial round of waves costs as much as a full one — the shortest segments
-        // whose waves fit one round (16 per CU at its 99 VGPRs; 4 GiB batch: 24 windows, 4064 waves)
-        const int64_t cap_waves = (int64_t)ctx->n_cu * 16;
-        auto waves_for = [&](int wn) {
-            int64_t wv = 0;
-            for (int b = 0; b < nblocks; b++) {
-                const int64_t ns = std::max<int64_t>(1, ((int64_t)len[b] + (int64_t)wn * unit - 1) / ((int64_t)wn * unit));
-                wv += (ns + kWaveSegs - 1) / kWaveSegs;
-            }
-            return wv;
-        };
-        wins = kSegMinWin;
-        while (wins < kSegMaxWinF && waves_for(wins) > cap_waves) wins++;
-    }
-    (void)total;
+    if (wins_env > 0) wins = std::max(kSegMinWin, std::min(kSegMaxWin, wins_env));
     const int seg_len = wins * unit;
     int seg0 = 0, wave0 = 0;
     for (int b = 0; b < nblocks; b++) {
@@ -616,28 +588,6 @@ int host::prepare_blocks(hdrf_ctx *ctx, Slot &S, int32_t nblocks, const uint8_t 
         if (int rc = dalloc(ctx, &S.d_spec, words)) return rc;
         S.spec_words = words;
     }
-    if (ctx->fused) {
-        if (!S.d_need)
-            if (int rc = dalloc(ctx, &S.d_need, (size_t)ctx->max_batch * ctx->cap_blk)) return rc;
-        if (!S.d_nlist)
-            if (int rc = dalloc(ctx, &S.d_nlist, (size_t)ctx->max_batch * ctx->cap_blk)) return rc;
-        if (!S.d_gmneed)
-            if (int rc = dalloc(ctx, &S.d_gmneed, (size_t)ctx->max_batch)) return rc;
-        if (words * ctx->HW > S.sdig_words) {
-            (void)hipFree(S.d_sdig);
-            S.d_sdig = nullptr;
-            S.sdig_words = 0;
-            if (int rc = dalloc(ctx, &S.d_sdig, words * ctx->HW)) return rc;
-            S.sdig_words = words * ctx->HW;
-        }
-        if ((size_t)seg0 + 1 > S.bdig_segs) {
-            (void)hipFree(S.d_bdig);
-            S.d_bdig = nullptr;
-            S.bdig_segs = 0;
-            if (int rc = dalloc(ctx, &S.d_bdig, ((size_t)seg0 + 1) * ctx->HW)) return rc;
-            S.bdig_segs = (size_t)seg0 + 1;
-        }
-    }
     return 0;
 }
 
@@ -665,30 +615,22 @@ static uint32_t close_bound(const hdrf_cfg &c, uint64_t bytes)
 // The front of a batch, as the single-GPU submit and the node-global front launch both enqueue it:
 // the descriptors go up on G (after the packet copies when after_copy), chunking runs on W (its granule
 // pass on G), then the fingerprints on A once the walk is done and the recipe copies of the slot's
-// previous batch have read d_dig.  fused: the fused front writes d_dig on W already, so W waits for
-// those copies too, and the SHA pass takes only the chunks marked in d_need (each block's last one,
-// repairs, fallbacks).  mw / ma: the stage markers of W and A.
+// previous batch have read d_dig.  mw / ma: the stage markers of W and A.
 int host::enqueue_front(hdrf_ctx *ctx, Slot &S, int nblocks, hipStream_t W, hipStream_t G, hipStream_t A, Marker *mw,
-                        Marker *ma, bool after_copy, bool fused)
+                        Marker *ma, bool after_copy)
 {
     const hdrf_cfg &c = ctx->cfg;
     if (after_copy) HIPCK(hipStreamWaitEvent(G, S.copy_done, 0));
     HIPCK(hipMemcpyAsync(S.d_blocks, S.h_desc, sizeof(BlockDesc) * nblocks, hipMemcpyHostToDevice, G));
-    if (fused && S.recipe_pending) HIPCK(hipStreamWaitEvent(W, S.recipe_done, 0));
-    const FusedFront fz{c.hasher, S.d_sdig, S.d_bdig, S.d_dig, S.d_need, S.d_gmneed};
     HIPCK(launch_chunking(S.d_blocks, nblocks, S.max_len, S.max_nseg, S.total_waves, S.total_segs,
                           chunk_scratch(S, c.compressor), c.window, c.max_chunk, S.d_spec, S.spec_cap, S.d_meta, S.d_bst,
-                          S.d_off, ctx->cap_blk, S.d_err, W, mw, G, S.gmax_done, fused ? &fz : nullptr));
+                          S.d_off, ctx->cap_blk, S.d_err, W, mw, G, S.gmax_done));
     mw->mark(W);
     HIPCK(hipEventRecord(S.walk_done, W));
     HIPCK(hipStreamWaitEvent(A, S.walk_done, 0));
     if (S.recipe_pending) HIPCK(hipStreamWaitEvent(A, S.recipe_done, 0));
-    if (fused)
-        HIPCK(launch_sha_need(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, S.d_need,
-                              S.d_nlist, A, ma));
-    else
-        HIPCK(launch_sha(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, ctx->sha_long, A,
-                         ma));
+    HIPCK(launch_sha(c.hasher, S.d_blocks, nblocks, S.d_off, S.d_bst, ctx->cap_blk, S.d_dig, S.d_queue, ctx->sha_long, A,
+                     ma));
     ma->mark(A);
     return 0;
 }
@@ -745,7 +687,7 @@ int host::submit(hdrf_ctx *ctx, int32_t nblocks, const uint8_t *const *dev_data,
     Marker mw, ma;
     mw.ev = ctx->timing ? S.evW : nullptr;
     ma.ev = ctx->timing ? S.evA : nullptr;
-    if (int rc = enqueue_front(ctx, S, nblocks, W, G, A, &mw, &ma, after_copy, ctx->fused)) return rc;
+    if (int rc = enqueue_front(ctx, S, nblocks, W, G, A, &mw, &ma, after_copy)) return rc;
     HIPCK(hipEventRecord(S.front_done, A));
     // ---- back, index part, in block order on stream B: claim .. decide, then idx_finalize takes the
     // batch-local state out of the index (designated chunks, block counts, entries cleared), so the

@@ -90,7 +90,7 @@ struct WalkCfg {
     int size;      // block length
     int w;         // window (700)
     int maxlen;    // forced-cut length (1,000,000)
-    const uint8_t *gm;   // the block's granule maxima (gmax_kernel), for long searches
+    const uint8_t *gm;   // the block's granule maxima (gmax2_kernel), for long searches
 };
 
 enum : int { kWindow = 0, kSearchFF = 1, kSearchGen = 2 };
@@ -373,9 +373,8 @@ __device__ __forceinline__ bool process_view(const WalkCfg &c, Chain &ch, const 
             else { ch.ended = true; return false; }
         } else {
             ch.q = max(ch.q, T + 2048);                                // continue after the advance
-            if (c.gm && ch.lim > T + 4096) {
-                // long search: the granule maxima say where the next candidate byte can be (without
-                // them — the fused front computes none — the search goes on tile by tile)
+            if (ch.lim > T + 4096) {
+                // long search: the granule maxima say where the next candidate byte can be
                 const int q2 = gm_skip(c.gm, ch.q, ch.lim, ch.state == kSearchFF ? 0xffu : ch.m);
                 if (q2 >= T + 4096) { ch.q = min(q2, ch.lim); ch.jump = true; }
             }
@@ -475,36 +474,6 @@ __device__ __forceinline__ bool walk_chain(const WalkCfg &c, int p, bool first, 
 //     speculative walk that reads every byte; it is HBM-bound.
 constexpr int kGmPerWg = 4096;           // granules per workgroup (64 KiB of data, 16 per thread)
 
-template <bool NT>
-__global__ void __launch_bounds__(256) gmax_kernel(const BlockDesc *__restrict__ blocks, uint8_t *__restrict__ gm,
-                                                   int gstride, int prio)
-{
-    if (prio) __builtin_amdgcn_s_setprio(2);        // HDRF_SETPRIO bit 4: ahead of SHA's VALU stream
-    const BlockDesc bd = blocks[blockIdx.y];
-    const int64_t ngran = (int64_t)((bd.len + 15) >> 4);
-    const int64_t g0 = (int64_t)blockIdx.x * kGmPerWg;
-    if (g0 >= ngran) return;
-    const uint8_t *base = bd.data;
-    HDRF_GLOBAL uint8_t *out = gptr_w<uint8_t>(gm + (size_t)blockIdx.y * gstride);
-    const int t = threadIdx.x;
-    uint4 v[16];
-    if ((g0 + kGmPerWg) * 16 <= (int64_t)bd.readable) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) v[i] = ld16_t<NT>(base + (g0 + 256 * i + t) * 16);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int64_t g = g0 + 256 * i + t;
-            v[i] = g < ngran ? load16_guard(base, g * 16, (int64_t)bd.readable) : make_uint4(0, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const int64_t g = g0 + 256 * i + t;
-        if (g < ngran) out[g] = (uint8_t)gmax16(bias(v[i]));
-    }
-}
-
 // gmax16 without the bias pass: the signed maximum of the 16 bytes from packed signed 16-bit maxima
 // (a 16-bit signed compare orders by its high byte first, so the high byte of a v_pk_max_i16 result is
 // the signed maximum of the high bytes), odd bytes from the raw words, even bytes from the words
@@ -522,15 +491,12 @@ __device__ __forceinline__ uint32_t gmax16_s(uint4 v)
     return (uint32_t)(max(hi, lo) + 128);                         // biased: signed order == unsigned order
 }
 
-// 1a'. the same pass, 15 VALU per granule, and the 16 granule bytes of a thread (256 apart) staged
-// through LDS so each thread writes one 16-B word of consecutive maxima (1 store instead of 16).
-// COND (the fused front): only the blocks whose cond[b] is set (a boundary of theirs went to the
-// repair walk, whose long searches and the sequential fallback read the maxima)
-template <bool NT, bool COND = false>
+// The pass: 15 VALU per granule, and the 16 granule bytes of a thread (256 apart) staged through LDS
+// so each thread writes one 16-B word of consecutive maxima (1 store instead of 16).
+template <bool NT>
 __global__ void __launch_bounds__(256) gmax2_kernel(const BlockDesc *__restrict__ blocks, uint8_t *__restrict__ gm,
-                                                    int gstride, int prio, const int *__restrict__ cond = nullptr)
+                                                    int gstride, int prio)
 {
-    if (COND && cond[blockIdx.y] == 0) return;
     if (prio) __builtin_amdgcn_s_setprio(2);
     __shared__ __attribute__((aligned(16))) uint8_t s_g[kGmPerWg];
     const BlockDesc bd = blocks[blockIdx.y];
@@ -656,14 +622,6 @@ __device__ __forceinline__ uint32_t range16(int lo, int hi)      // bits lo..hi 
     const uint32_t b = hi < 0 ? 0u : (hi >= 15 ? 0xffffu : ((2u << hi) - 1u));
     return a & b;
 }
-__device__ __forceinline__ void load_gm(uint32_t (&d)[kGmWin], const uint8_t *p)
-{
-#pragma unroll
-    for (int i = 0; i < kGmWin / 4; i++) {
-        const uint4 v = ld16(p + 16 * i);
-        d[4 * i] = v.x; d[4 * i + 1] = v.y; d[4 * i + 2] = v.z; d[4 * i + 3] = v.w;
-    }
-}
 
 typedef __attribute__((address_space(3))) volatile uint16_t lds_u16v;
 typedef __attribute__((address_space(3))) volatile uint8_t lds_u8v;
@@ -677,12 +635,6 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // next unit is prefetched into registers at the end of a chunk step once the window has moved into
 // the ring's second unit (after the step's raw load was waited for, so that wait never covers the
 // prefetch), and written into the ring when the window reaches it.  12 KiB of LDS per wave.
-#ifndef HDRF_COOP
-#define HDRF_COOP 1                      // wave-cooperative list and offsets copies (0: per-lane rows, the A/B
-#endif                                   // baseline; profiles/r06_coop*_ab.txt)
-#ifndef HDRF_WALK_LINE
-#define HDRF_WALK_LINE 1                 // (0: half-line units, the A/B baseline; profiles/r06_walkline*_ab.txt)
-#endif
 constexpr int kRingU = 4 * kGmWin;       // granules per ring unit (= the window)
 constexpr int kRingDw = 2 * kGmWin;      // ring dwords per lane (lanes read at their own, unrelated
 constexpr int kRingPitch = kRingDw;      // offsets, so rows are not padded)
@@ -692,10 +644,8 @@ struct GmRing {
     int w0 = 0;                          // the last window start
     int pfg = -1;                        // granule of the unit held in pf (-1: none)
     uint4 pf[kGmWin / 4];
-#if HDRF_WALK_LINE
     int pfg2 = -1;                       // the unit held in pf2: a line's second half (-1: none)
     uint4 pf2[kGmWin / 4];
-#endif
     __device__ __forceinline__ void put(int g, const uint4 (&v)[kGmWin / 4])
     {
 #pragma unroll
@@ -711,32 +661,28 @@ struct GmRing {
         for (int i = 0; i < kGmWin / 4; i++) v[i] = ld16(gmb + g + 16 * i);
         put(g, v);
     }
-    // HDRF_WALK_LINE (build flag, default 1): a unit that starts a 128-B line is fetched with the line's
-    // second half, which is kept in pf2 for the next unit (a unit is half a line: fetched apart, a line's
-    // halves came from memory twice when the first was evicted between the lane's chunk steps; half the
-    // ring's scattered 16-B load instructions).  Walk counted bytes 1.20 -> 1.11 GB per batch; config 2
+    // A unit that starts a 128-B line is fetched with the line's second half, which is kept in pf2 for the
+    // next unit (a unit is half a line: fetched apart, a line's halves came from memory twice when the first
+    // was evicted between the lane's chunk steps; half the ring's scattered 16-B load instructions).  Against
+    // half-line units (profiles/r06_walkline*_ab.txt): walk counted bytes 1.20 -> 1.11 GB per batch; config 2
     // 1098 / 1105 / 1110 vs 1058 / 1057 / 1056 and 1113 / 1118 / 1116 vs 1114 / 1104 / 1106 GB/s on two boxes
     __device__ __forceinline__ void prefetch(const uint8_t *gmb)
     {
         if (on && pfg != rb + 2 * kRingU && w0 >= rb + kRingU / 2) {
             pfg = rb + 2 * kRingU;
-#if HDRF_WALK_LINE
             if (pfg2 == pfg) {
 #pragma unroll
                 for (int i = 0; i < kGmWin / 4; i++) pf[i] = pf2[i];
                 pfg2 = -1;
                 return;
             }
-#endif
 #pragma unroll
             for (int i = 0; i < kGmWin / 4; i++) pf[i] = ld16(gmb + pfg + 16 * i);
-#if HDRF_WALK_LINE
             if ((pfg & 127) == 0) {
 #pragma unroll
                 for (int i = 0; i < kGmWin / 4; i++) pf2[i] = ld16(gmb + pfg + kRingU + 16 * i);
                 pfg2 = pfg + kRingU;
             }
-#endif
         }
     }
     bool on = true;                      // false: HDRF_WALK_RING=0, the maxima straight from memory (A/B)
@@ -758,9 +704,7 @@ struct GmRing {
         if (W0 < rb || W0 > rb + kRingU) {
             if (W0 <= rb + 2 * kRingU) {                          // the window moved on by one unit
                 if (pfg == rb + 2 * kRingU) put(pfg, pf);
-#if HDRF_WALK_LINE
                 else if (pfg2 == rb + 2 * kRingU) put(pfg2, pf2);
-#endif
                 else fill(gmb, rb + 2 * kRingU);
                 rb += kRingU;
             } else {                                              // first use, or a long search jumped
@@ -932,11 +876,10 @@ __global__ void __launch_bounds__(256) lane_walk_kernel(const BlockDesc *__restr
         if (overflow) active = false;
     }
     if (overflow && real) atomicOr(err, 64);
-#if HDRF_COOP
     {
         // the wave's lists, written together: its 63 segments' lists are consecutive rows of `cap`
         // words (segment G at G * cap), so the lanes store the rows' words in order (coalesced) instead
-        // of each lane walking its own row (63 scattered streams of ~15 stores)
+        // of each lane walking its own row (63 scattered streams of ~15 stores; profiles/r06_coop*_ab.txt)
         const int nreal = min(kWaveSegs, nseg - wl * kWaveSegs);
         uint32_t *rows = spec + (size_t)(bd.seg0 + wl * kWaveSegs) * cap;
         int j = l / cap, i = l - (l / cap) * cap;
@@ -948,13 +891,8 @@ __global__ void __launch_bounds__(256) lane_walk_kernel(const BlockDesc *__restr
             if (i >= cap) { i -= cap; j++; }
         }
     }
-#endif
     if (real) {
         const int G = bd.seg0 + k;
-#if !HDRF_COOP
-        uint32_t *list = spec + (size_t)G * cap;
-        for (int i = 0; i < n; i++) list[i] = (uint32_t)s + (uint32_t)vcuts[l * kLdsCuts + i];
-#endif
         if (n_main < 0) n_main = n;
         // (SegMeta records staged through LDS and stored together: +1.5 % run second, -2.3 % run first,
         // profiles/r06_meta_ab.txt; not adopted)
@@ -1034,7 +972,7 @@ __global__ void __launch_bounds__(64) lane_repair_kernel(const BlockDesc *__rest
         const bool first = n == 0 && s_k == 0;
         WalkCfg W;
         W.base = bd.data; W.avail = (int)min(bd.readable, (uint64_t)0x7fffffff); W.size = (int)bd.len;
-        W.w = w; W.maxlen = maxlen; W.gm = gm ? gm + (size_t)bi * gstride : nullptr;
+        W.w = w; W.maxlen = maxlen; W.gm = gm + (size_t)bi * gstride;
         if (!emit) {
             KeepSink sink;
             sink.cap = kRepairCuts; sink.cnt = 0; sink.stage = 0;
@@ -1225,7 +1163,6 @@ __global__ void __launch_bounds__(256) stitch_count_kernel(const BlockDesc *__re
     const int nj = nr;                                     // local indices: jump j0 + i at i
     SegMeta *mt = meta + bd.seg0;
     int from = 0, cnt = 0, ext = -1;
-    bool entered_by_jump = false;
     if (k < nseg && k <= term) {
         const int i0 = j0 < 0 ? 1 : 0;                     // local entry 0 is jump j0 (none when j0 < 0)
         int lo = i0, hi = nj;                              // last jump with source < k
@@ -1237,7 +1174,6 @@ __global__ void __launch_bounds__(256) stitch_count_kernel(const BlockDesc *__re
             over = tgt > k;                                // jumped over
             target = tgt == k;
         }
-        entered_by_jump = target;
         if (!over) {
             const SegMeta m = mt[k];
             if (k == 0) from = 0;
@@ -1255,7 +1191,6 @@ __global__ void __launch_bounds__(256) stitch_count_kernel(const BlockDesc *__re
         mt[k].cp_n = ext >= 0 ? ext : cnt;                 // list cuts; the repair's cuts follow (emit)
         mt[k].pad[0] = cnt;
         mt[k].pad[1] = ext;
-        mt[k].pad[2] = k == 0 ? 0 : (entered_by_jump ? 2 : 1);   // how the path entered (fused digests)
     }
     uint32_t total;
     (void)wg_excl_scan((uint32_t)cnt, s_w, total);
@@ -1288,62 +1223,12 @@ __global__ void __launch_bounds__(64) stitch_scan_kernel(const BlockDesc *__rest
     }
 }
 
-// With the fused pass (lanehash.hip, sdig != nullptr) the digests of the copied list cuts move to the
-// batch's digest rows too and their need[] flags are cleared: list cut from + i of segment k ends a
-// chunk of lane k's chain that starts on the path for i > 0, and for i == 0 at the block start (k == 0);
-// the first cut after a sync is the chunk lane k - 1 cut up to the shared cut (bdig[k]), on the path
-// when segment k - 1 contributed a cut of its own (or is segment 0).  A jump target's first cut, the
-// repair's cuts and the fallback's are hashed by the fix-up pass (sha.hip).
-// the wave's 64 segments four at a time, a 16-lane group per segment, one digest row per lane: the
-// loads of up to 48 rows per segment are issued before any store (one memory round trip per four
-// segments; one segment per step with a word per lane left the stitch 0.55 ms slower per batch)
-template <int HW>
-__device__ __forceinline__ void copy_digests_wave(int n_l, int G, int from, int dst, bool head, int k, int cap,
-                                                  const uint32_t *__restrict__ sdig, const uint32_t *__restrict__ bdig,
-                                                  uint32_t *__restrict__ dig, uint8_t *__restrict__ need)
-{
-    const int l = lane_id(), r = l & 15;
-    for (int j0 = 0; j0 < 64; j0 += 4) {
-        const int j = j0 + (l >> 4);
-        const int nj = __shfl(n_l, j, 64);
-        if (!ballot64(nj > 0)) continue;
-        const int Gj = __shfl(G, j, 64), fj = __shfl(from, j, 64), dj = __shfl(dst, j, 64), kj = __shfl(k, j, 64);
-        const bool hj = __shfl((int)head, j, 64) != 0;
-        uint32_t v[3][HW];
-        bool ok[3];
-#pragma unroll
-        for (int u = 0; u < 3; u++) {
-            const int i = r + 16 * u;
-            ok[u] = i < nj && (i > 0 || kj == 0 || hj);
-            const uint32_t *ds = (i > 0 || kj == 0) ? sdig + ((size_t)Gj * cap + fj + i) * HW : bdig + (size_t)Gj * HW;
-#pragma unroll
-            for (int w = 0; w < HW; w++) v[u][w] = ok[u] ? ds[w] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < 3; u++) {
-            const int i = r + 16 * u;
-            if (!ok[u]) continue;
-#pragma unroll
-            for (int w = 0; w < HW; w++) dig[(size_t)(dj + i) * HW + w] = v[u][w];
-            need[dj + i] = 0;
-        }
-        for (int i = r + 48; i < nj; i += 16) {           // (longer lists than kSegMaxWinF allows: none)
-#pragma unroll
-            for (int w = 0; w < HW; w++) dig[(size_t)(dj + i) * HW + w] = sdig[((size_t)Gj * cap + fj + i) * HW + w];
-            need[dj + i] = 0;
-        }
-    }
-}
 __global__ void __launch_bounds__(256) stitch_copy_kernel(const BlockDesc *__restrict__ blocks,
                                                           SegMeta *__restrict__ meta,
                                                           const uint32_t *__restrict__ spec, int cap,
                                                           const uint32_t *__restrict__ wgsum, int maxw,
                                                           const BlockState *__restrict__ bst,
-                                                          uint32_t *__restrict__ offsets, int cap_blk,
-                                                          const uint32_t *__restrict__ sdig = nullptr,
-                                                          const uint32_t *__restrict__ bdig = nullptr,
-                                                          uint32_t *__restrict__ dig = nullptr,
-                                                          uint8_t *__restrict__ need = nullptr, int HW = 0)
+                                                          uint32_t *__restrict__ offsets, int cap_blk)
 {
     __shared__ uint32_t s_w[4];
     const int b = blockIdx.y, t = threadIdx.x;
@@ -1359,14 +1244,7 @@ __global__ void __launch_bounds__(256) stitch_copy_kernel(const BlockDesc *__res
     if (k < nseg && cnt > 0) {
         const int ext = meta[G].pad[1];
         if (ext >= 0) meta[G].ext_dst = (int)dst + ext;  // the repair's cuts (emit pass)
-#if !HDRF_COOP
-        const int n = meta[G].cp_n, from = meta[G].cp_from;
-        const uint32_t *src = spec + (size_t)G * cap + from;
-        uint32_t *out = offsets + (size_t)b * cap_blk + dst;
-        for (int i = 0; i < n; i++) out[i] = src[i];
-#endif
     }
-#if HDRF_COOP
     {                                                     // (uniform) the pieces, 16 lanes per segment
         const bool mine = k < nseg && cnt > 0;
         const int n_l = mine ? meta[G].cp_n : 0, from_l = mine ? meta[G].cp_from : 0;
@@ -1386,16 +1264,6 @@ __global__ void __launch_bounds__(256) stitch_copy_kernel(const BlockDesc *__res
             for (int i = r + 48; i < nj; i += 16) orow[dj + i] = spec[(size_t)Gj * cap + fj + i];
         }
     }
-#endif
-    if (sdig) {                                           // (uniform) the fused pass's digests
-        const bool mine = k < nseg && cnt > 0;
-        const int n_l = mine ? meta[G].cp_n : 0, from_l = mine ? meta[G].cp_from : 0;
-        const bool head = mine && (k == 0 || (meta[G].pad[2] == 1 && (k == 1 || meta[G - 1].pad[0] > 0)));
-        uint32_t *drow = dig + (size_t)b * cap_blk * HW;
-        uint8_t *nrow = need + (size_t)b * cap_blk;
-        if (HW == 5) copy_digests_wave<5>(n_l, G, from_l, (int)dst, head, k, cap, sdig, bdig, drow, nrow);
-        else copy_digests_wave<7>(n_l, G, from_l, (int)dst, head, k, cap, sdig, bdig, drow, nrow);
-    }
 }
 
 // 4. fallback + drop-last/append-size: one wave per block.  A block whose path ends at a failed
@@ -1405,8 +1273,7 @@ __global__ void __launch_bounds__(256) stitch_copy_kernel(const BlockDesc *__res
 __global__ void __launch_bounds__(64) spec_fallback_kernel(const BlockDesc *__restrict__ blocks, int w, int maxlen,
                                                            uint32_t *__restrict__ offsets, int cap_blk,
                                                            BlockState *__restrict__ bst, const uint8_t *__restrict__ gm,
-                                                           int gstride, int *__restrict__ err, int prio,
-                                                           uint8_t *__restrict__ need = nullptr)
+                                                           int gstride, int *__restrict__ err, int prio)
 {    if (prio) __builtin_amdgcn_s_setprio(3);        // latency-bound chain: issue before co-running waves
 
     const int b = blockIdx.x;
@@ -1416,7 +1283,7 @@ __global__ void __launch_bounds__(64) spec_fallback_kernel(const BlockDesc *__re
     if (s.fail_dst >= 0) {
         WalkCfg W;
         W.base = bd.data; W.avail = (int)min(bd.readable, (uint64_t)0x7fffffff); W.size = (int)bd.len;
-        W.w = w; W.maxlen = maxlen; W.gm = gm ? gm + (size_t)b * gstride : nullptr;
+        W.w = w; W.maxlen = maxlen; W.gm = gm + (size_t)b * gstride;
         const bool first = s.fail_dst == 0;
         const int p0 = first ? 0 : (int)off[s.fail_dst - 1];
         ListSink sink;
@@ -1438,7 +1305,6 @@ __global__ void __launch_bounds__(64) spec_fallback_kernel(const BlockDesc *__re
         off[n - 1] = (uint32_t)bd.len;
         s.n_chunks = n;
         bst[b] = s;
-        if (need) need[(size_t)b * cap_blk + n - 1] = 1;  // [off[n - 2], len): not a chunk any lane cut
     }
 }
 
@@ -1454,15 +1320,13 @@ int setprio_mask()
     return m;
 }
 
-// The back of both fronts: repair (count), stitch path / count / scan / copy, repair (emit), sequential
-// fallback.  gm: the granule maxima the repair walk and the fallback skip by (nullptr: none were
-// computed); fz: the fused front's digests, carried by the stitch copy and the fallback.
+// The chunking tail after the lane walk: repair (count), stitch path / count / scan / copy, repair (emit), sequential
+// fallback.  gm: the granule maxima the repair walk and the fallback skip by.
 // 2048 repair waves loop over the queue, one per workgroup: the chain's small kernels start in
 // whatever wave slots the co-running kernels leave (a 4-wave workgroup needs four on one CU)
 static hipError_t launch_repair_stitch(const BlockDesc *d_blocks, int nblocks, const ChunkScratch &X, int w, int maxlen,
                                        uint32_t *spec, int spec_cap, SegMeta *meta, BlockState *bst, uint32_t *offsets,
-                                       int cap_blk, int *err, hipStream_t st, int maxw, int prio, const uint8_t *gm,
-                                       const FusedFront *fz)
+                                       int cap_blk, int *err, hipStream_t st, int maxw, int prio, const uint8_t *gm)
 {
     const int rgrid = 2048;
     const int p1 = (prio >> 1) & 1;
@@ -1475,62 +1339,22 @@ static hipError_t launch_repair_stitch(const BlockDesc *d_blocks, int nblocks, c
     hipLaunchKernelGGL(stitch_scan_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, X.path, X.wgsum, maxw, bst,
                        cap_blk, err);
     hipLaunchKernelGGL(stitch_copy_kernel, dim3(maxw, nblocks), dim3(256), 0, st, d_blocks, meta, spec, spec_cap,
-                       X.wgsum, maxw, bst, offsets, cap_blk, fz ? (const uint32_t *)fz->sdig : nullptr,
-                       fz ? (const uint32_t *)fz->bdig : nullptr, fz ? fz->dig : nullptr, fz ? fz->need : nullptr,
-                       fz ? (fz->hasher == 0 ? 5 : 7) : 0);
+                       X.wgsum, maxw, bst, offsets, cap_blk);
     hipLaunchKernelGGL(lane_repair_kernel, dim3(rgrid), dim3(64), 0, st, d_blocks, nblocks, X.rq, X.rq_count, X.rq_cap,
                        w, maxlen, spec, spec_cap, meta, offsets, cap_blk, gm, X.gstride, 1, p1, X.rqkeep);
     hipLaunchKernelGGL(spec_fallback_kernel, dim3(nblocks), dim3(64), 0, st, d_blocks, w, maxlen, offsets,
-                       cap_blk, bst, gm, X.gstride, err, p1, fz ? fz->need : nullptr);
+                       cap_blk, bst, gm, X.gstride, err, p1);
     return hipGetLastError();
-}
-
-// The fused front (HDRF_FUSED=1): lanehash.hip's pass cuts and hashes the lane segments; the granule
-// maxima are computed only when a boundary was queued for the repair walk (whose long searches and the
-// sequential fallback read them); then the stitch as in the two-pass front, carrying the digests.
-// Stage markers: the granule slot stays empty, the walk slot times the fused pass, the stitch slot the
-// conditional granule pass, repair, stitch and fallback.
-static hipError_t launch_fused_front(const BlockDesc *d_blocks, int nblocks, int64_t max_len, int total_waves, int nsegs,
-                                     const ChunkScratch &X, int w, int maxlen, uint32_t *spec, int spec_cap,
-                                     SegMeta *meta, BlockState *bst, uint32_t *offsets, int cap_blk, int *err,
-                                     hipStream_t st, Marker *mk, const FusedFront &fz, int maxw)
-{
-    mk->mark(st);
-    hipError_t e = hipMemsetAsync(X.rq_count, 0, sizeof(int), st);
-    if (e == hipSuccess) e = hipMemsetAsync(X.irr, 0, sizeof(uint32_t) * (size_t)(nsegs / 32 + 2), st);
-    if (e == hipSuccess) e = hipMemsetAsync(fz.need, 1, (size_t)nblocks * cap_blk, st);
-    if (e == hipSuccess) e = hipMemsetAsync(fz.gm_need, 0, sizeof(int) * (size_t)nblocks, st);
-    if (e != hipSuccess) return e;
-    const int prio = setprio_mask();
-    mk->mark(st);
-    if ((e = launch_lane_hash(fz.hasher, d_blocks, nblocks, total_waves, w, maxlen, spec, spec_cap, meta, X.rq, X.rq_count,
-                              X.rq_cap, X.irr, fz.sdig, fz.bdig, fz.gm_need, err, st)) != hipSuccess)
-        return e;
-    mk->mark(st);
-    // HDRF_FUSED_GM=1: the granule maxima of the blocks with a repaired boundary (the repair walk's
-    // long searches skip by them); default none: a boundary of every 4 GiB batch's blocks goes to the
-    // repair walk, so the pass ran over the whole batch (4.56 GB, profiles/r06_fz_traffic.json)
-    static const bool fz_gm = env_int("HDRF_FUSED_GM", 0) != 0;
-    const uint8_t *gm = fz_gm ? X.gm : nullptr;
-    if (fz_gm) {
-        const int gx = (int)(((max_len + 15) / 16 + kGmPerWg - 1) / kGmPerWg);
-        hipLaunchKernelGGL((gmax2_kernel<true, true>), dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, st, d_blocks, X.gm,
-                           X.gstride, (prio >> 4) & 1, (const int *)fz.gm_need);
-    }
-    return launch_repair_stitch(d_blocks, nblocks, X, w, maxlen, spec, spec_cap, meta, bst, offsets, cap_blk, err, st, maxw,
-                                prio, gm, &fz);
 }
 
 hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_len, int max_nseg, int total_waves,
                            int nsegs, const ChunkScratch &X, int w, int maxlen, uint32_t *spec, int spec_cap,
                            SegMeta *meta, BlockState *bst, uint32_t *offsets, int cap_blk, int *err, hipStream_t st,
-                           Marker *mk, hipStream_t stg, hipEvent_t gdone, const FusedFront *fz)
+                           Marker *mk, hipStream_t stg, hipEvent_t gdone)
 {
     if ((max_len + 15) / 16 + 4 * kGmWin > X.gstride) return hipErrorInvalidValue;
     const int maxw = (max_nseg + 255) / 256;
     if (maxw > X.maxw) return hipErrorInvalidValue;
-    if (fz) return launch_fused_front(d_blocks, nblocks, max_len, total_waves, nsegs, X, w, maxlen, spec, spec_cap, meta,
-                                      bst, offsets, cap_blk, err, st, mk, *fz, maxw);
     const bool split = stg && stg != st && gdone;     // granule pass on its own stream, the walk waits for it
     hipStream_t sg = split ? stg : st;
     mk->mark(sg);
@@ -1542,16 +1366,10 @@ hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_l
     // all SHA lanes (sha.hip), bit 4 the granule pass, bit 5 place (store.hip))
     const int prio = setprio_mask();
     const int gx = (int)(((max_len + 15) / 16 + kGmPerWg - 1) / kGmPerWg);
-    // HDRF_GMAX_V: 2 (default) gmax2 (15 VALU per granule, one 16-B store per thread), 1 the round-2 pass
-    static const int gver = env_int("HDRF_GMAX_V", 2);
-    if (gver == 2 && (stream_knobs() & 1))
+    if (stream_knobs() & 1)
         hipLaunchKernelGGL(gmax2_kernel<true>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
-    else if (gver == 2)
-        hipLaunchKernelGGL(gmax2_kernel<false>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
-    else if (stream_knobs() & 1)
-        hipLaunchKernelGGL(gmax_kernel<true>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
     else
-        hipLaunchKernelGGL(gmax_kernel<false>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
+        hipLaunchKernelGGL(gmax2_kernel<false>, dim3(gx > 0 ? gx : 1, nblocks), dim3(256), 0, sg, d_blocks, X.gm, X.gstride, (prio >> 4) & 1);
     mk->mark(sg);
     if (split) {
         if ((e = hipEventRecord(gdone, sg)) != hipSuccess || (e = hipStreamWaitEvent(st, gdone, 0)) != hipSuccess)
@@ -1572,6 +1390,6 @@ hipError_t launch_chunking(const BlockDesc *d_blocks, int nblocks, int64_t max_l
                        X.gm, X.gstride, w, maxlen, spec, spec_cap, meta, X.rq, X.rq_count, X.rq_cap, X.irr, err, ring_on, prio & 1);
     mk->mark(st);
     return launch_repair_stitch(d_blocks, nblocks, X, w, maxlen, spec, spec_cap, meta, bst, offsets, cap_blk, err, st, maxw,
-                                prio, X.gm, nullptr);
+                                prio, X.gm);
 }
 }  // namespace hdrf

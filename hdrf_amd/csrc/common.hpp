@@ -27,10 +27,6 @@ constexpr int kRepairBytes = 2 << 20;  // ... or this many bytes past its start
 constexpr int kRqKeep = 16384;       // repair-queue entries whose cuts the count pass keeps (64 words each)
 constexpr int kSegMinWin = 4;        // seg_len bounds, in units of window + 2 (702 B)
 constexpr int kSegMaxWin = 20;        // seg_len / 702 + 2 + kLaneOver <= kLdsCuts
-// the fused chunk + fingerprint pass (lanehash.hip) sizes its segments for one round of its waves,
-// which needs longer segments on a 4 GiB batch (24 windows): its own list bound
-constexpr int kSegMaxWinF = 28;
-constexpr int kLdsCutsF = 40;        // kSegMaxWinF + 2 + kLaneOver <= kLdsCutsF
 
 // Index entry: 64 B.  tag = the table generation ("epoch", 1..255) in bits 56..63 over the first 7
 // digest bytes; an entry whose tag carries another epoch is EMPTY, so a fresh index (hdrf_reset)
@@ -120,7 +116,7 @@ struct SegMeta {
     int32_t cp_from;         // stitch plan: copy list[cp_from, cp_from + cp_n) to the block's offsets
     int32_t cp_n;
     int32_t cp_dst;          // unused
-    int32_t pad[3];          // stitch scratch: piece size, repair-cut position in the piece
+    int32_t pad[3];          // stitch scratch: piece size, repair-cut position in the piece; [2] unused (zero)
 };
 
 // Stitch path of one block (stitch_path_kernel): on-path jumps, the terminal segment, fallback flag.
@@ -192,11 +188,6 @@ template <class T>
 __device__ __forceinline__ const HDRF_GLOBAL T *gptr(const void *p)
 {
     return (const HDRF_GLOBAL T *)(p);
-}
-template <class T>
-__device__ __forceinline__ HDRF_GLOBAL T *gptr_w(void *p)
-{
-    return (HDRF_GLOBAL T *)(p);
 }
 
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));

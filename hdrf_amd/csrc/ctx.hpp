@@ -39,11 +39,6 @@ struct Slot {
     BlockDesc *d_blocks = nullptr;
     uint32_t *d_spec = nullptr;
     SegMeta *d_meta = nullptr;
-    // the fused front (HDRF_FUSED=1, lanehash.hip): per-cut and per-boundary digests, fix-up marks
-    uint32_t *d_sdig = nullptr, *d_bdig = nullptr, *d_nlist = nullptr;
-    int *d_gmneed = nullptr;
-    uint8_t *d_need = nullptr;
-    size_t sdig_words = 0, bdig_segs = 0;
     uint8_t *d_gm = nullptr;                  // granule maxima [B][gstride] (chunking pass 1)
     int gstride = 0;
     int64_t max_len = 0;                      // longest block of the batch in this slot
@@ -161,8 +156,7 @@ struct hdrf_ctx {
     // chunks >= 64 KiB were seen in the last completed batch: sha_full hashes them on dedicated
     // lanes (sha.hip); off otherwise, where the scan for them costs config 2 ~3 %
     bool sha_long = false;
-    bool fused = false;                              // the fused chunk + fingerprint front (fused_front)
-    int n_cu = 256;                                  // compute units of the device (the fused pass's segment sizing)
+    int n_cu = 256;                                  // compute units of the device (the scrub hash grid)
     int max_batch = 0, cap_blk = 0, ntiles = 0, ev_cap = 0, closed_cap = 0, coll_cap = 0;
     Slot sl[kSlots];
     uint64_t nsub = 0, nwait = 0;  // batches submitted / completed
@@ -365,9 +359,9 @@ int prepare_blocks(hdrf_ctx *ctx, Slot &S, int32_t nblocks, const uint8_t *const
                    const uint64_t *readable);
 StoreParams store_params(const hdrf_ctx *ctx, int nblocks);
 // the front of a batch (single-GPU and node-global alike): descriptors up on G, chunking on W,
-// fingerprints on A; fused: the fused chunk + fingerprint front
+// fingerprints on A
 int enqueue_front(hdrf_ctx *ctx, Slot &S, int nblocks, hipStream_t W, hipStream_t G, hipStream_t A, Marker *mw, Marker *ma,
-                  bool after_copy = false, bool fused = false);
+                  bool after_copy = false);
 // enqueue one batch: front on stream A, back on stream B
 int submit(hdrf_ctx *ctx, int32_t nblocks, const uint8_t *const *dev_data, const uint64_t *len,
            const uint64_t *readable, const uint64_t *block_ids, bool after_copy = false);

@@ -263,71 +263,6 @@ __global__ void __launch_bounds__(256) sha_carry_kernel(const BlockDesc *__restr
     sha_chunk_body<HW, true>(blocks, offsets, bst, cap_blk, digests, queue, thr, prio);
 }
 
-
-// The fused front's fix-up (lanehash.hip): the chunks still marked in need[] — each block's last chunk
-// (the drop-last rule), a jump target's first, the repair walk's and the sequential fallback's — are
-// compacted into a list (block << 26 | chunk), then hashed one lane each.  Config 2 leaves about one
-// per block; iterating the per-block queues over every chunk instead cost 0.53 ms per batch.
-__global__ void __launch_bounds__(256) need_list_kernel(const BlockState *__restrict__ bst, int cap_blk,
-                                                        const uint8_t *__restrict__ need, uint32_t *__restrict__ list,
-                                                        uint32_t *__restrict__ count)
-{
-    const int b = blockIdx.y;
-    const int n = bst[b].n_chunks;
-    if ((int)blockIdx.x * 1024 >= n) return;
-    const int k0 = blockIdx.x * 1024 + 4 * threadIdx.x;
-    const uint8_t *nb = need + (size_t)b * cap_blk;
-    uint32_t f = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        if (k0 + j < n && nb[k0 + j]) f |= 1u << j;
-    const uint32_t c = (uint32_t)__popc(f);
-    const uint32_t incl = wave_incl_scan(c);
-    uint32_t base = 0;
-    if (lane_id() == 63 && incl) base = atomicAdd(count, incl);
-    base = (uint32_t)__shfl((int)base, 63, 64) + incl - c;
-    for (int j = 0; j < 4; j++)
-        if (f & (1u << j)) list[base++] = ((uint32_t)b << 26) | (uint32_t)(k0 + j);
-}
-
-template <int HW>
-__global__ void __launch_bounds__(256) sha_list_kernel(const BlockDesc *__restrict__ blocks,
-                                                       const uint32_t *__restrict__ offsets, int cap_blk,
-                                                       uint32_t *__restrict__ digests, const uint32_t *__restrict__ list,
-                                                       const uint32_t *__restrict__ count)
-{
-    const uint32_t nl = *count;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) {
-        const uint32_t e = list[i];
-        const int lb = (int)(e >> 26), lk = (int)(e & 0x3ffffffu);
-        const uint32_t *lo = offsets + (size_t)lb * cap_blk;
-        const uint32_t s0 = lk ? lo[lk - 1] : 0u;
-        const uint32_t len = lo[lk] - s0, T = len >> 6, nb = (len + 8) / 64 + 1;
-        uint32_t st[8], bi = 0;
-        set_iv<HW>(st);
-        const BlockDesc &bd = blocks[lb];
-        while (bi < nb) sha_iter<HW>(bd.data, bd.readable, s0, len, T, nb, bi, st);
-        store_digest<HW>(digests + ((size_t)lb * cap_blk + lk) * HW, st);
-    }
-}
-
-hipError_t launch_sha_need(int hasher, const BlockDesc *d_blocks, int nblocks, const uint32_t *offsets,
-                           const BlockState *bst, int cap_blk, uint32_t *digests, uint32_t *queue, const uint8_t *need,
-                           uint32_t *list, hipStream_t st, Marker *mk)
-{
-    if (nblocks > 64) return hipErrorInvalidValue;
-    if (hipError_t e = hipMemsetAsync(queue, 0, sizeof(uint32_t) * 67, st)) return e;
-    mk->mark(st);
-    const int tiles = (cap_blk + 1023) / 1024;
-    hipLaunchKernelGGL(need_list_kernel, dim3(tiles, nblocks), dim3(256), 0, st, bst, cap_blk, need, list, queue + 66);
-    with_digest_words(hasher, [&](auto hw) {
-        hipLaunchKernelGGL(sha_list_kernel<decltype(hw)::value>, dim3(64), dim3(256), 0, st, d_blocks, offsets, cap_blk,
-                           digests, list, queue + 66);
-    });
-    mk->mark(st);
-    return hipGetLastError();
-}
-
 hipError_t launch_sha(int hasher, const BlockDesc *d_blocks, int nblocks, const uint32_t *offsets,
                       const BlockState *bst, int cap_blk, uint32_t *digests, uint32_t *queue, bool long_lanes,
                       hipStream_t st, Marker *mk)

@@ -1,5 +1,5 @@
 // sha_core.hpp — SHA-1 / SHA-224 compression, FIPS 180-4 padding and the per-lane window loads
-// shared by the fingerprint kernels (sha.hip) and the fused chunk + fingerprint pass (lanehash.hip).
+// shared by the fingerprint kernels (sha.hip) and the scrub / verified-read hash kernel (verify.hip).
 // Reference: DN/utilities.java:98-137 (nayuki native compress + FIPS 180-4 padding).
 #pragma once
 #include "launchers.hpp"

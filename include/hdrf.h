@@ -353,7 +353,7 @@ int hdrf_corpus_fill_kind(hdrf_ctx *ctx, uint8_t *dev, const uint32_t *roots_hos
  * the streams the stages run on (cfg.timing = 1): [0] lane_walk_kernel, [1] stitch (repair / path /
  * count / scan / copy / fallback), [2] sha_full_kernel, [3] sha_tail_kernel, [4] idx_claim_kernel,
  * [5] idx_apply_kernel, [6] idx_slow+decide, [7] new-byte scans, [8] flush_kernel, [9] place_kernel,
- * [10] lz4 (compressor 2), [11] gmax_kernel (granule maxima); node-global contexts also
+ * [10] lz4 (compressor 2), [11] gmax2_kernel (granule maxima); node-global contexts also
  * [12] local aggregation + X1 records, [13] owner claim..finish, [14] gx_decide, [15] flush function,
  * [16] device allocator scan, [17] placement (part 1), [18] commit, and the gaps on the back stream
  * that the caller's exchanges fill: [19] X1 (+ the host), [20] X2, [21] descriptor all-gather,
