@@ -1,12 +1,13 @@
 // api_views.hip — libhdrf C-ABI: what a DataNode reads back or restores once batches have completed:
 // index views, restore (index, allocator, recipes), recipes and block lengths, container read / load /
-// unload, the durable-container drain, and reconstruction.
+// unload, the durable-container drain, reconstruction, and the batched ranged reads.
 //
 // The views drain the pipeline and write nothing but the grown scratch buffers (d_rd, d_stage).
 // Restore writes the index table, the allocator (d_alloc, h_alloc, have_alloc), containers and
 // recipes; load / unload write ctx->loaded; hdrf_drain_containers writes the drain bookkeeping
 // (pend_closed, undrained, handed) and the drain job list (h_xfer).
 #include "ctx.hpp"
+#include "read_plan.hpp"
 
 // ---- index views ------------------------------------------------------------------------
 static void encode_value(const IndexEntry &e, uint8_t v[11])
@@ -577,4 +578,146 @@ extern "C" int64_t hdrf_reconstruct_block_verified(hdrf_ctx *ctx, uint64_t block
     HDRF_LOCK(ctx);
     if (!ctx || !bad_chunk) return HDRF_E_INVAL;
     return reconstruct_block_body(ctx, block_id, out, cap, bad_chunk);
+}
+
+// ---- batched, ranged reads (readv.hip; the arithmetic is read_plan.hpp's) -----------------------
+// T, the bytes of output one gather wave fills.  HDRF_READ_TILE (4096, 8192 or 16384; read at every
+// call, changes no result) is the knob scripts/read_speed.py measures with.
+static uint32_t read_tile()
+{
+    const int t = env_int("HDRF_READ_TILE", (int)kReadTile);
+    return t == 4096 || t == 8192 || t == 16384 ? (uint32_t)t : kReadTile;
+}
+
+// hdrf_read_batch with the arguments checked, the lock held and the batches in flight completed.
+// Everything is enqueued on ctx->st; the one host wait follows the status read-back.
+static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
+{
+    if (n == 0) return 0;
+    const uint32_t T = read_tile();
+    const int H = ctx->H;
+    std::vector<ReadDesc> desc((size_t)n);
+    std::vector<int64_t> pre((size_t)n, 0);              // what the host decides: < 0 fails the request
+    std::vector<uint64_t> dig_off((size_t)n, 0);         // caller-supplied digests: offset in the scratch
+    uint64_t dig_bytes = 0;
+    ReadPrefix px;
+    for (int i = 0; i < n; i++) {
+        const hdrf_read_req &q = req[i];
+        ReadDesc &d = desc[(size_t)i];
+        d = ReadDesc{};
+        uint64_t size = 0, cnt = 0, clen = 0;
+        if (q.recipe) {
+            if (q.recipe_len < 4 || (q.recipe_len - 4) % H) pre[i] = HDRF_E_INVAL;
+            else {
+                size = ((uint64_t)q.recipe[0] << 24) | (q.recipe[1] << 16) | (q.recipe[2] << 8) | q.recipe[3];
+                cnt = (uint64_t)(q.recipe_len - 4) / H;
+            }
+        } else {
+            auto it = ctx->recipes.find((uint32_t)q.block_id);
+            if (it == ctx->recipes.end()) pre[i] = HDRF_E_NOTFOUND;
+            else {
+                size = (uint64_t)ctx->lengths[(uint32_t)q.block_id];
+                cnt = it->second.n;
+                d.dig = (uint64_t)(uintptr_t)(ctx->rchunks[it->second.chunk] + it->second.off);
+            }
+        }
+        if (!pre[i] && !read_clip(size, q.offset, q.length, &clen)) pre[i] = HDRF_E_INVAL;
+        if (!pre[i] && clen && !q.dev_out) pre[i] = HDRF_E_INVAL;
+        if (!pre[i] && cnt == 0 && size != 0) pre[i] = HDRF_E_DEVICE;      // a recipe without digests
+        if (!pre[i] && cnt >= (1ull << 31)) pre[i] = HDRF_E_INVAL;
+        if (pre[i]) cnt = clen = 0;                      // no rows, no tiles: the kernels pass it by
+        else {
+            d.out = (uint64_t)(uintptr_t)q.dev_out;
+            d.n = (uint32_t)cnt;
+            d.size = (uint32_t)size;
+            d.off = (uint32_t)q.offset;
+            d.len = (uint32_t)clen;
+            if (q.recipe && cnt) {
+                dig_off[i] = dig_bytes;
+                dig_bytes += cnt * H;                    // H is a multiple of 4: the words stay aligned
+            }
+        }
+        if (!px.add((uint32_t)cnt, d.out, clen, T, &d.row0, &d.tile0))
+            return set_err(ctx, HDRF_E_CAPACITY, "read batch: too many chunks or tiles for one call");
+    }
+    Readable rd;
+    readable_list(ctx, rd);
+    const uint32_t ncont = (uint32_t)rd.cid.size();
+    const ReadLayout L = read_layout((uint32_t)n, ncont, dig_bytes, px.rows, (uint32_t)rv_chunk_bytes());
+    if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, L.total)) return rc == HDRF_E_HIP ? HDRF_E_NOMEM : rc;
+    uint8_t *R = ctx->d_rd;
+    std::vector<uint8_t> up(L.upload, 0);
+    for (int i = 0; i < n; i++) {
+        if (pre[i] || !req[i].recipe || !desc[i].n) continue;
+        desc[i].dig = (uint64_t)(uintptr_t)(R + L.o_dig + dig_off[i]);
+        std::memcpy(up.data() + L.o_dig + dig_off[i], req[i].recipe + 4, (size_t)desc[i].n * H);
+    }
+    std::memcpy(up.data() + L.o_desc, desc.data(), desc.size() * sizeof(ReadDesc));
+    if (ncont) {
+        std::memcpy(up.data() + L.o_cid, rd.cid.data(), (size_t)ncont * 4);
+        std::memcpy(up.data() + L.o_base, rd.base.data(), (size_t)ncont * 8);
+    }
+    hipStream_t st = ctx->st;
+    std::vector<int> status((size_t)n, 0);
+    HIPCK(hipMemcpyAsync(R, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(R + L.o_status, 0, (size_t)n * 4, st));
+    HIPCK(launch_readv(ctx->cfg.hasher, (const ReadDesc *)(R + L.o_desc), n, (uint32_t)px.rows, (uint32_t)px.tiles, T,
+                       ctx->d_tab, ctx->cfg.index_log2, tag_mask(ctx), (const uint32_t *)(R + L.o_cid),
+                       (const uint64_t *)(R + L.o_base), (int)ncont, R + L.o_rows, (int *)(R + L.o_status), st));
+    HIPCK(hipMemcpyAsync(status.data(), R + L.o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    int first = 0;
+    for (int i = 0; i < n; i++) {
+        int64_t r = pre[i];
+        const char *why = r == HDRF_E_NOTFOUND ? "no recipe for this block (keep_recipes?)"
+                          : r == HDRF_E_DEVICE ? "recipe without digests" : "bad recipe, offset past the block's end or no output";
+        if (!r && (status[i] & kReadNotFound)) {
+            r = HDRF_E_NOTFOUND;
+            why = "a recipe digest is not in the index, or a container of the range is not readable";
+        } else if (!r && (status[i] & kReadDevice)) {
+            r = HDRF_E_DEVICE;
+            why = "chunk lengths do not add up to the recipe size";
+        }
+        req[i].result = r ? r : (int64_t)desc[i].len;
+        if (r && !first) first = set_err(ctx, (int)r, "read request " + std::to_string(i) + ": " + why);
+    }
+    return first;
+}
+
+static_assert(sizeof(hdrf_read_req) == 56, "hdrf_read_req: ctypes mirror ReadReq in hdrf_amd/lib.py");
+
+extern "C" int hdrf_read_batch(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !req) return HDRF_E_INVAL;
+    if (n < 0 || n > HDRF_READ_MAX_REQS) return set_err(ctx, HDRF_E_INVAL, "read batch: n outside [0, HDRF_READ_MAX_REQS]");
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "ranged reads on node-global contexts");
+    if (int rc = drain(ctx)) return rc;
+    return read_batch_body(ctx, n, req);
+}
+
+extern "C" int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out,
+                                   int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "ranged reads on node-global contexts");
+    if (int rc = drain(ctx)) return rc;                  // blocks in flight first: their recipes are SET
+    uint64_t clen = 0;
+    auto it = ctx->lengths.find((uint32_t)block_id);
+    if (it != ctx->lengths.end() && ctx->recipes.count((uint32_t)block_id)) {
+        if (!read_clip((uint64_t)it->second, offset, length, &clen))
+            return set_err(ctx, HDRF_E_INVAL, "offset past the block's end");
+        if (cap < (int64_t)clen || (clen && !out)) return set_err(ctx, HDRF_E_CAPACITY, "needs " + std::to_string(clen) + " bytes");
+        if (int rc = grow(ctx, &ctx->d_stage, &ctx->stage_cap, clen + 4096)) return rc;
+    }                                                    // (no recipe: the request reports it)
+    hdrf_read_req q{};
+    q.block_id = block_id;
+    q.offset = offset;
+    q.length = length;
+    q.dev_out = ctx->d_stage;
+    const int rc = read_batch_body(ctx, 1, &q);
+    if (rc) return rc;
+    if (q.result > 0) HIPCK(hipMemcpy(out, ctx->d_stage, (size_t)q.result, hipMemcpyDeviceToHost));
+    return q.result;
 }

@@ -244,6 +244,15 @@ hipError_t launch_rd_gather(const void *chunks, int n, const uint64_t *bases, ui
 hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                               unsigned long long key, const uint32_t *cids, const uint64_t *bases, int ncont,
                               void *chunks, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather);
+// batched, ranged reads (readv.hip): nreq requests (ReadDesc, read_plan.hpp) with nrows chunk rows
+// (rv_chunk_bytes each, the RdChunk layout) and ntiles output tiles of T bytes in all.  Lookup, scan
+// and gather are enqueued back to back; status[r] != 0 (cleared by the caller) tells which requests
+// failed (kReadNotFound / kReadDevice) and wrote nothing.
+struct ReadDesc;
+size_t rv_chunk_bytes();
+hipError_t launch_readv(int hasher, const ReadDesc *req, int nreq, uint32_t nrows, uint32_t ntiles, uint32_t T,
+                        const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *cids,
+                        const uint64_t *bases, int ncont, void *rows, int *status, hipStream_t st);
 // fingerprint scrub / verified reads (verify.hip).  Counters of one table slice (scrub) or one
 // rebuilt block (verified read), zeroed by the caller before the launches.
 struct VfCounters {

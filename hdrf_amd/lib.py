@@ -37,10 +37,12 @@ EXPORTS = [
     "hdrf_set_lzop_mtime", "hdrf_gx_flush_fn_dev", "hdrf_gx_alloc_scan_dev", "hdrf_gx_place_launch",
     "hdrf_gx_place_wait", "hdrf_gx_sync", "hdrf_reset_async",
     "hdrf_scrub", "hdrf_reconstruct_verified", "hdrf_reconstruct_block_verified",
+    "hdrf_read_batch", "hdrf_read_range",
 ]
 
 ALLOC_STATE_BYTES = 128     # HDRF_ALLOC_STATE_BYTES
 PIPELINE_DEPTH = 5          # HDRF_PIPELINE_DEPTH: batches in flight
+READ_MAX_REQS = 256         # HDRF_READ_MAX_REQS: requests of one hdrf_read_batch call
 
 
 # per-stage timers of hdrf_stage_times (kernel names in parentheses)
@@ -92,6 +94,12 @@ class BadChunk(ctypes.Structure):           # hdrf_bad_chunk (44 B)
 
 class ScrubStats(ctypes.Structure):         # hdrf_scrub_stats (40 B)
     _fields_ = [(n, ctypes.c_int64) for n in ("entries", "checked", "skipped", "bytes", "bad")]
+
+
+class ReadReq(ctypes.Structure):            # hdrf_read_req (56 B)
+    _fields_ = [("block_id", ctypes.c_uint64), ("recipe", ctypes.c_void_p), ("recipe_len", ctypes.c_int64),
+                ("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dev_out", ctypes.c_void_p),
+                ("result", ctypes.c_int64)]
 
 
 class GxLayout(ctypes.Structure):
@@ -180,6 +188,9 @@ def load():
         "hdrf_reconstruct_block_verified": (ctypes.c_int64, [_vp, ctypes.c_uint64, _u8p, ctypes.c_int64, _i64p]),
         "hdrf_scrub": (ctypes.c_int64, [_vp, ctypes.c_int64, ctypes.POINTER(BadChunk), ctypes.c_int64,
                                         ctypes.POINTER(ScrubStats)]),
+        "hdrf_read_batch": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(ReadReq)]),
+        "hdrf_read_range": (ctypes.c_int64, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u8p,
+                                             ctypes.c_int64]),
         "hdrf_gx_read_locate": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp]),
         "hdrf_gx_flush_fn": (ctypes.c_int64, [_vp, _vp, ctypes.c_int64]),
         "hdrf_gx_alloc_scan": (ctypes.c_int32, [_vp, _vp, _vp, _u8p, _u8p]),
@@ -585,6 +596,40 @@ class Context:
             return self._ck_verified(self.L.hdrf_reconstruct_verified(self._h, _p(r), r.size, dev_out, cap,
                                                                       ctypes.byref(bad)), bad)
         return self._ck(self.L.hdrf_reconstruct(self._h, _p(r), r.size, dev_out, cap))
+
+    def read_batch(self, reqs):
+        """hdrf_read_batch: up to READ_MAX_REQS byte ranges served by one set of launches.  reqs:
+        (block, offset, length, dev_out) tuples, block = a block id (the stored recipe) or a recipe's
+        bytes; dev_out = a device address (any alignment).  Returns the list of per-request results
+        (bytes written, or a negative HDRF_E_* code: one failing request does not stop the others).
+        Raises HdrfError only on a call-level failure; read_batch_code is the call's return value
+        (0, or the code of the lowest-numbered failing request)."""
+        n = len(reqs)
+        arr = (ReadReq * max(n, 1))()
+        keep = []
+        for q, (blk, off, length, dev) in zip(arr, reqs):
+            if isinstance(blk, (bytes, bytearray, memoryview, np.ndarray)):
+                r = np.frombuffer(bytes(blk), np.uint8).copy()
+                keep.append(r)
+                q.recipe, q.recipe_len = r.ctypes.data, r.size
+            else:
+                q.block_id = int(blk)
+            q.offset, q.length, q.dev_out, q.result = int(off), int(length), dev, 0
+        rc = self.L.hdrf_read_batch(self._h, n, arr)
+        self.read_batch_code = rc
+        results = [q.result for q in arr[:n]]
+        if rc < 0 and not any(r == rc for r in results):
+            self._ck(rc)
+        return results
+
+    def read_range(self, block_id, offset, length):
+        """hdrf_read_range: bytes [offset, offset + length) of a stored block, clipped to its end, as
+        np.uint8 (BlockSender's startOffset / length; only those bytes are gathered and copied)."""
+        # (the block may belong to a batch still in flight, whose length only the call itself learns)
+        cap = max(0, min(int(length), int(self.cfg.max_block_bytes)))
+        out = np.empty(max(cap, 1), np.uint8)
+        m = self._ck(self.L.hdrf_read_range(self._h, block_id, offset, length, _p(out), cap))
+        return out[:m].copy()
 
     def scrub(self, container=None):
         """hdrf_scrub: every index entry whose container is readable re-hashed from the container's

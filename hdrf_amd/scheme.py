@@ -48,6 +48,13 @@ class HipReductionScheme(ReductionScheme):
             return self.ctx.reconstruct_block(block_id, verify=True).tobytes()
         return self.ctx.reconstruct_block(block_id).tobytes()
 
+    def read(self, block_id, offset, length):
+        """Bytes [offset, offset + length) of the block, clipped to its end (BlockSender's startOffset /
+        length, DN/BlockSender.java:612-619): only the chunks under the range are gathered."""
+        return self.ctx.read_range(block_id, offset, length).tobytes()
+
+    read_range = read
+
     def scrub(self, container=None):
         """Re-hash every stored chunk whose container is readable: (stats, bad chunks)."""
         return self.ctx.scrub(container)

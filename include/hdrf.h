@@ -315,6 +315,46 @@ int64_t hdrf_reconstruct_verified(hdrf_ctx *ctx, const uint8_t *recipe, int64_t 
                                   int64_t cap, int64_t *bad_chunk);
 int64_t hdrf_reconstruct_block_verified(hdrf_ctx *ctx, uint64_t block_id, uint8_t *out, int64_t cap, int64_t *bad_chunk);
 
+/* Batched, ranged reads.  An HDFS read names a byte range: BlockSender is built with startOffset and
+ * length, and the reference rebuilds the whole block and seeks into it (DN/BlockSender.java:612-619:
+ * new DataConstructor(id, t1data), then new ByteArrayInputStream(dConstructor.data, (int) offset, ...)).
+ * hdrf_read_batch serves n <= HDRF_READ_MAX_REQS requests, each one byte range of one block, with one
+ * set of launches and one host wait; only the chunks that overlap a range are copied.
+ *   When it runs   a view: it completes the batches in flight and applies a pending hdrf_reset_async,
+ *                  as hdrf_reconstruct does, and takes the context lock.  Single-node contexts
+ *                  (HDRF_E_UNSUPPORTED when n_ranks > 1).
+ *   Ranges         offset > size: that request gets HDRF_E_INVAL.  offset == size or length == 0: 0
+ *                  bytes.  A length past the block's end is clipped to size - offset.
+ *   Outputs        a request that succeeds writes exactly [dev_out, dev_out + result): no byte before
+ *                  or after that span is touched.  A request that fails writes nothing (never a partial
+ *                  block, per request).  The output ranges of different requests must not overlap (the
+ *                  result is undefined if they do).
+ *   Failures       one failing request does not stop the others: every req[i].result is filled; the
+ *                  call returns 0 when every request succeeded, otherwise the code of the
+ *                  lowest-numbered failing request, which hdrf_last_error names.  Call-level failures
+ *                  (NULL arguments, n outside [0, HDRF_READ_MAX_REQS], allocation or HIP failure)
+ *                  return their code and touch no output.
+ *   HDRF_E_NOTFOUND  there is no recipe for block_id; or a recipe digest is absent from the index,
+ *                  wherever it sits in the recipe (the offsets cannot be computed without it); or a
+ *                  chunk that overlaps the requested range sits in a container that is not readable
+ *                  (chunks outside the range may: a ranged read needs only the containers it touches).
+ *   HDRF_E_DEVICE  the chunk lengths of the recipe do not add up to its BE32 size.
+ * hdrf_read_range is one request through the same path for a stored recipe, with the clipped range
+ * copied to host memory (only those bytes travel); HDRF_E_CAPACITY when cap is below the clipped
+ * length.  Returns the bytes written. */
+#define HDRF_READ_MAX_REQS 256
+typedef struct {
+    uint64_t block_id;       /* recipe from the context's store (keep_recipes / hdrf_recipe_load) ... */
+    const uint8_t *recipe;   /* ... unless non-NULL: [BE32 size | digests], host memory, as hdrf_reconstruct takes */
+    int64_t  recipe_len;
+    uint64_t offset;         /* first byte wanted (BlockSender's startOffset) */
+    uint64_t length;         /* bytes wanted; clipped to size - offset */
+    uint8_t *dev_out;        /* device memory, any alignment, `clipped length` bytes, no slack needed */
+    int64_t  result;         /* out: bytes written (the clipped length), or a negative HDRF_E_* */
+} hdrf_read_req;
+int hdrf_read_batch(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req);
+int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out, int64_t cap);
+
 /* The same read on a node-global context (cfg.n_ranks = G > 1): the node's ONE index is
  * partitioned over the ranks, and a container's bytes are spread over the ranks that placed
  * chunks into it, so every rank takes part (hdrf_amd/node.py NodeRank.reconstruct_block; the

@@ -115,6 +115,24 @@ class HipReductionScheme final : public ReductionScheme {
         return out;
     }
 
+    // bytes [offset, offset + length) of the block, clipped to its end (BlockSender's startOffset and
+    // length, DN/BlockSender.java:612-619): only the chunks under the range are gathered and copied
+    std::vector<uint8_t> read_range(uint64_t block_id, uint64_t offset, uint64_t length)
+    {
+        const int64_t len = hdrf_block_length(ctx_, block_id);
+        if (len < 0) check((int)len);
+        const uint64_t left = offset <= (uint64_t)len ? (uint64_t)len - offset : 0;
+        std::vector<uint8_t> out((size_t)(length < left ? length : left));
+        const int64_t n = hdrf_read_range(ctx_, block_id, offset, length, out.data(), (int64_t)out.size());
+        if (n < 0) check((int)n);
+        out.resize((size_t)n);
+        return out;
+    }
+    std::vector<uint8_t> read(uint64_t block_id, uint64_t offset, uint64_t length)
+    {
+        return read_range(block_id, offset, length);
+    }
+
     // every index entry whose container is readable re-hashed against its key: the bad chunks
     // (sorted by container, start, digest) and, when st is given, the counts
     std::vector<hdrf_bad_chunk> scrub(int64_t container = -1, hdrf_scrub_stats *st = nullptr)

@@ -168,6 +168,16 @@ public final class HipReductionScheme extends ReductionScheme {
   }
 
   /**
+   * Bytes [offset, offset + length) of the block, clipped to its end (BlockSender's startOffset and
+   * length, BlockSender.java:612-619): only the chunks under the range are gathered on the GPU and only
+   * those bytes cross to the host (hdrf_read_range).
+   */
+  @Override
+  public byte[] readRange(long blockId, long offset, long length) throws IOException {
+    return readRange0(ctx, blockId, offset, length);
+  }
+
+  /**
    * The block scanner: every index entry whose container is resident or loaded is re-hashed from
    * the container's bytes and compared with its key; returns the number of bad chunks.
    */
@@ -194,6 +204,7 @@ public final class HipReductionScheme extends ReductionScheme {
       throws IOException;
   private static native byte[] reconstruct0(long ctx, long blockId) throws IOException;
   private static native byte[] reconstructVerified0(long ctx, long blockId) throws IOException;
+  private static native byte[] readRange0(long ctx, long blockId, long offset, long length) throws IOException;
   private static native long scrub0(long ctx) throws IOException;
   private static native void reduce0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void submit0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;

@@ -17,6 +17,23 @@ public abstract class ReductionScheme implements AutoCloseable {
   /** Rebuild the block bytes from the recipe stored under {@code blockId}. */
   public abstract byte[] reconstruct(long blockId) throws IOException;
 
+  /**
+   * Bytes [offset, offset + length) of the block, clipped to its end: what BlockSender serves for a
+   * read that starts at {@code startOffset} (BlockSender.java:612-619).  This default does what the
+   * reference does, rebuild the whole block and seek into it; a backend that can gather only the
+   * chunks under the range overrides it.
+   */
+  public byte[] readRange(long blockId, long offset, long length) throws IOException {
+    byte[] data = reconstruct(blockId);
+    if (offset < 0 || length < 0 || offset > data.length) {
+      throw new IOException("range starts past the end of block " + blockId);
+    }
+    int n = (int) Math.min(length, data.length - offset);
+    byte[] out = new byte[n];
+    System.arraycopy(data, (int) offset, out, 0, n);
+    return out;
+  }
+
   /** Logical length of a reduced block (recipe head). */
   public abstract long length(long blockId) throws IOException;
 

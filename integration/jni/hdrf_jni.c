@@ -297,6 +297,26 @@ JNIEXPORT jbyteArray JNICALL JFN(reconstructVerified0)(JNIEnv *env, jclass cls, 
     return out;
 }
 
+/* Bytes [offset, offset + length) of the block, clipped to its end: BlockSender's startOffset and
+ * length (DN/BlockSender.java:612-619) without the whole-block rebuild and copy (hdrf_read_range). */
+JNIEXPORT jbyteArray JNICALL JFN(readRange0)(JNIEnv *env, jclass cls, jlong h, jlong id, jlong offset, jlong length)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int64_t len = hdrf_block_length(ctx, (uint64_t)id);
+    if (len < 0) { throw_io(env, ctx, (int)len); return NULL; }
+    if (offset < 0 || length < 0 || offset > len) { throw_io(env, ctx, HDRF_E_INVAL); return NULL; }
+    int64_t want = length < len - offset ? length : len - offset;
+    uint8_t *tmp = (uint8_t *)malloc((size_t)(want ? want : 1));
+    if (!tmp) { throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+    int64_t n = hdrf_read_range(ctx, (uint64_t)id, (uint64_t)offset, (uint64_t)length, tmp, want);
+    if (n < 0) { free(tmp); throw_io(env, ctx, (int)n); return NULL; }
+    jbyteArray out = (*env)->NewByteArray(env, (jsize)n);
+    if (out) (*env)->SetByteArrayRegion(env, out, 0, (jsize)n, (const jbyte *)tmp);
+    free(tmp);
+    return out;
+}
+
 /* The block scanner of a content-addressed store: every index entry whose container is readable
  * re-hashed against its key; returns how many are bad (hdrf_scrub). */
 JNIEXPORT jlong JNICALL JFN(scrub0)(JNIEnv *env, jclass cls, jlong h)
