@@ -248,6 +248,23 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
 
 __device__ __forceinline__ unsigned long long ballot64(bool p) { return __ballot(p); }
 
+// this lane's rank among the lanes of mask m
+__device__ __forceinline__ int wave_rank(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+
+// one slot of *counter for every lane of `m` (the lanes that call with want): one atomic per wave
+__device__ __forceinline__ uint32_t wave_append(uint32_t *counter, bool want)
+{
+    const unsigned long long m = ballot64(want);
+    if (!m) return 0u;
+    uint32_t base = 0;
+    if (lane_id() == (int)__builtin_ctzll(m)) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, (int)__builtin_ctzll(m), 64);
+    return base + (uint32_t)wave_rank(m);
+}
+
 // Reserve one slot of counter counts[d] for every lane that wants one (256 threads; every thread of
 // the workgroup calls it, in uniform control flow): the lanes count in LDS, then one global atomic
 // per (workgroup, counter) takes the workgroup's slots (d < G <= 64; s_cnt / s_base: LDS [64]).  The

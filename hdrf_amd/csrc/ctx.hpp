@@ -1,7 +1,8 @@
 // ctx.hpp — the context behind the C-ABI (include/hdrf.h) and the host functions its translation
 // units share.  Internal: included only by the api*.hip files (api.hip core and batch pipeline,
 // api_rx.hip packet receive, api_stream.hip stream codecs, api_gx.hip node-global phases,
-// api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub); each of them names in its header comment
+// api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub, api_gc.hip block deletion and
+// index garbage collection); each of them names in its header comment
 // the context state it may write.  Everything here but hdrf_ctx itself lives in hdrf::host, hidden
 // from the library's dynamic symbols.
 #pragma once

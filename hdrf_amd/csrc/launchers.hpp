@@ -288,6 +288,34 @@ hipError_t launch_vf_hash_block(int hasher, const void *chunks, int n, const uin
                                 uint64_t block_bytes, VfCounters *C, int wgs, hipStream_t st);
 hipError_t launch_vf_rows(int hasher, const uint32_t *bad, uint32_t from, uint32_t n, const IndexEntry *tab,
                           uint64_t slot0, VfBadRow *out, hipStream_t st);
+// index garbage collection (gc.hip; the flat-range arithmetic is gc_plan.hpp's).  Counters of one
+// collection, zeroed by the caller before the launches.
+struct GcJob;
+struct GcCounters {
+    unsigned long long missing;          // recipe digests absent from the index (mark)
+    unsigned long long entries, kept, dropped, kept_bytes, dropped_bytes;   // live entries (sweep)
+    uint32_t n_rows;                     // survivor rows written
+    uint32_t n_unknown;                  // live entries whose container id is not in the list
+    uint32_t err;                        // 1: a container id of 2^24 or more, 2: survivor rows past the capacity
+    uint32_t n_marked;                   // marked slots (counted when survivor rows are wanted)
+};
+struct GcContCount {                     // per container of the sorted id list
+    unsigned long long kept_chunks, kept_bytes, dropped_chunks, dropped_bytes;
+};
+// mark: one lane per recipe digest of the nj jobs (+ sentinel) over `total` flat positions; the slot
+// of every digest found is set in `mark` (one bit per table slot, cleared by the caller)
+hipError_t launch_gc_mark(int hasher, const GcJob *jobs, uint32_t nj, uint64_t total, const IndexEntry *tab, int log2cap,
+                          unsigned long long key, uint32_t *mark, GcCounters *C, hipStream_t st);
+// sweep: one lane per table slot.  Live and marked: kept, appended to the survivor rows in the layout
+// launch_index_load reads (dw_rows: digest words, val_rows: 11-byte values; row_cap rows, none when
+// dw_rows is null); live and unmarked: dropped.  Both add to cc[] of their container (cids: sorted, ncont
+// ids); an id outside the list is set in `seen` (2^24 bits) and counted in n_unknown instead.
+// wg (kGcSweepMaxWgs words, needed with dw_rows): the marked slots of each workgroup's tiles, counted
+// first, give every workgroup the first row of its own.
+// mark == nullptr: only C->entries is counted (the check after a rebuild).
+hipError_t launch_gc_sweep(int hasher, const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *mark,
+                           const uint32_t *cids, int ncont, GcContCount *cc, uint32_t *seen, uint32_t *dw_rows,
+                           uint8_t *val_rows, uint64_t row_cap, uint32_t *wg, GcCounters *C, int wgs, hipStream_t st);
 hipError_t launch_corpus(uint8_t *dev, const uint32_t *d_roots, int64_t nblocks, int64_t spb, int64_t seg_bytes,
                          uint64_t seed, int mixed, hipStream_t st);
 

@@ -37,22 +37,6 @@ struct RdChunkV {            // read.hip RdChunk (rd_chunk_bytes() == 16, checke
     uint32_t slot, start, len, off;
 };
 
-__device__ __forceinline__ int vf_rank(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-
-// one slot of *counter for every lane of `m` (the lanes that call with want): one atomic per wave
-__device__ __forceinline__ uint32_t wave_append(uint32_t *counter, bool want)
-{
-    const unsigned long long m = ballot64(want);
-    if (!m) return 0u;
-    uint32_t base = 0;
-    if (lane_id() == (int)__builtin_ctzll(m)) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, (int)__builtin_ctzll(m), 64);
-    return base + (uint32_t)vf_rank(m);
-}
-
 // Persistent workgroups: workgroup x takes the 256-slot tiles x, x + gridDim.x, ... of the slice.
 // Items are compacted into an LDS batch first (ballot + mbcnt per wave, an LDS counter per
 // workgroup) and a batch leaves with ONE global atomic: with one global atomic per wave of 64
@@ -222,7 +206,7 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
                 }
                 if (cntP == 0) break;
             }
-            const int rank = vf_rank(idle), avail = cntP - head, idx = min(head + rank, 63);
+            const int rank = wave_rank(idle), avail = cntP - head, idx = min(head + rank, 63);
             const uint32_t q0 = (uint32_t)__shfl((int)p0, idx, 64), q1 = (uint32_t)__shfl((int)p1, idx, 64);
             const uint32_t q2 = (uint32_t)__shfl((int)p2, idx, 64), q3 = (uint32_t)__shfl((int)p3, idx, 64);
             if (!active && rank < avail) {

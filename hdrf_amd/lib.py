@@ -38,11 +38,13 @@ EXPORTS = [
     "hdrf_gx_place_wait", "hdrf_gx_sync", "hdrf_reset_async",
     "hdrf_scrub", "hdrf_reconstruct_verified", "hdrf_reconstruct_block_verified",
     "hdrf_read_batch", "hdrf_read_range",
+    "hdrf_block_delete", "hdrf_gc",
 ]
 
 ALLOC_STATE_BYTES = 128     # HDRF_ALLOC_STATE_BYTES
 PIPELINE_DEPTH = 5          # HDRF_PIPELINE_DEPTH: batches in flight
 READ_MAX_REQS = 256         # HDRF_READ_MAX_REQS: requests of one hdrf_read_batch call
+GC_DRY = 1                  # HDRF_GC_DRY: mark and account only
 
 
 # per-stage timers of hdrf_stage_times (kernel names in parentheses)
@@ -100,6 +102,16 @@ class ReadReq(ctypes.Structure):            # hdrf_read_req (56 B)
     _fields_ = [("block_id", ctypes.c_uint64), ("recipe", ctypes.c_void_p), ("recipe_len", ctypes.c_int64),
                 ("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dev_out", ctypes.c_void_p),
                 ("result", ctypes.c_int64)]
+
+
+class GcStats(ctypes.Structure):            # hdrf_gc_stats (80 B)
+    _fields_ = [(n, ctypes.c_int64) for n in ("recipes", "recipe_digests", "entries", "kept", "dropped", "kept_bytes",
+                                             "dropped_bytes", "missing", "containers", "dead_containers")]
+
+
+class GcContainer(ctypes.Structure):        # hdrf_gc_container (40 B)
+    _fields_ = [("id", ctypes.c_uint32), ("readable", ctypes.c_int32), ("kept_chunks", ctypes.c_int64),
+                ("kept_bytes", ctypes.c_int64), ("dropped_chunks", ctypes.c_int64), ("dropped_bytes", ctypes.c_int64)]
 
 
 class GxLayout(ctypes.Structure):
@@ -191,6 +203,9 @@ def load():
         "hdrf_read_batch": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(ReadReq)]),
         "hdrf_read_range": (ctypes.c_int64, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u8p,
                                              ctypes.c_int64]),
+        "hdrf_block_delete": (ctypes.c_int, [_vp, ctypes.c_uint64]),
+        "hdrf_gc": (ctypes.c_int64, [_vp, ctypes.c_int32, ctypes.POINTER(GcStats), ctypes.POINTER(GcContainer),
+                                     ctypes.c_int64]),
         "hdrf_gx_read_locate": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp]),
         "hdrf_gx_flush_fn": (ctypes.c_int64, [_vp, _vp, ctypes.c_int64]),
         "hdrf_gx_alloc_scan": (ctypes.c_int32, [_vp, _vp, _vp, _u8p, _u8p]),
@@ -653,6 +668,32 @@ class Context:
 
     def block_length(self, block_id):
         return self._ck(self.L.hdrf_block_length(self._h, block_id))
+
+    def block_delete(self, block_id):
+        """hdrf_block_delete (FsDatasetImpl.invalidate): forget a block's recipe and length.  The index
+        keeps its chunks until gc()."""
+        self._ck(self.L.hdrf_block_delete(self._h, block_id))
+
+    def gc(self, dry=False):
+        """hdrf_gc: drop every index entry that no remaining recipe names (dry=True: account only, the
+        index is not touched).  Returns (stats, rows): stats = dict(recipes, recipe_digests, entries, kept,
+        dropped, kept_bytes, dropped_bytes, missing, containers, dead_containers); rows = one
+        dict(id, readable, kept_chunks, kept_bytes, dropped_chunks, dropped_bytes) per container an index
+        entry named before the collection, sorted by id (kept_chunks == 0: the container is dead)."""
+        if not dry:                             # size the rows first: the collecting call must not truncate them
+            cap = self._ck(self.L.hdrf_gc(self._h, GC_DRY, None, None, 0)) + 64
+        else:
+            cap = 256
+        while True:
+            buf = (GcContainer * cap)()
+            st = GcStats()
+            n = self._ck(self.L.hdrf_gc(self._h, GC_DRY if dry else 0, ctypes.byref(st), buf, cap))
+            if n > cap and dry:
+                cap = n
+                continue
+            stats = {f: getattr(st, f) for f, _ in GcStats._fields_}
+            rows = [{f: getattr(r, f) for f, _ in GcContainer._fields_} for r in buf[:min(n, cap)]]
+            return stats, rows
 
     def container(self, cid):
         closed = ctypes.c_int32(0)

@@ -62,6 +62,14 @@ class HipReductionScheme(ReductionScheme):
     def length(self, block_id):
         return self.ctx.block_length(block_id)
 
+    def delete(self, block_id):
+        """Forget a block (FsDatasetImpl.invalidate); its chunks stay indexed until gc()."""
+        self.ctx.block_delete(block_id)
+
+    def gc(self, dry=False):
+        """Drop every index entry no remaining recipe names: (stats, per-container rows)."""
+        return self.ctx.gc(dry=dry)
+
     def recipe(self, block_id):
         return self.ctx.recipe(block_id)
 

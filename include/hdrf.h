@@ -374,6 +374,55 @@ int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint6
 int64_t hdrf_gx_read_locate(hdrf_ctx *ctx, const uint8_t *digests, int64_t n, uint32_t *loc);
 int64_t hdrf_gx_read_fill(hdrf_ctx *ctx, const uint32_t *loc, int64_t n, uint8_t *dev_out, int64_t cap);
 
+/* Block deletion and index garbage collection.  HDFS deletes blocks all the time: BPOfferService calls
+ * FsDatasetImpl.invalidate (DN/fsdataset/impl/FsDatasetImpl.java:2026-2100), which in the reference
+ * removes the 0-byte block file and its .meta and leaves the recipe, the chunks' index entries and the
+ * container bytes behind forever.
+ * hdrf_block_delete forgets a block: it completes the batches in flight (as the views do), then drops
+ * the block's recipe location and its length (so stream-mode blocks are covered too) and subtracts the
+ * recipe from hdrf_stats.recipe_bytes.  HDRF_E_NOTFOUND for a block the context does not know.
+ * Afterwards hdrf_recipe_get returns 0 and hdrf_block_length, hdrf_reconstruct_block* and hdrf_read_range
+ * return HDRF_E_NOTFOUND.  The index is not touched (the delete is cheap; collection happens later), and
+ * the recipe's bytes in the append-only device recipe store are not reclaimed: compacting that store is
+ * out of scope.
+ * hdrf_gc collects the index: the live set is the set of digests of all recipes the context holds; an
+ * index entry whose digest is in it is kept, every other live entry is dropped.
+ *   When it runs   it takes the context lock, completes the batches in flight and applies a pending
+ *                  hdrf_reset_async, like the other views and restores.  Single-node contexts
+ *                  (HDRF_E_UNSUPPORTED when n_ranks > 1).  HDRF_E_INVAL when cfg.keep_recipes == 0 (the
+ *                  context's recipes are then not the complete live set, and collecting would drop
+ *                  live chunks) and while a packet receive is open, as hdrf_reset.
+ *   Returns        the number of container rows: one for every container id that some index entry
+ *                  named before the collection; the first min(rows, cap) are written sorted by id.
+ *                  A container with kept_chunks == 0 is dead: the DataNode may delete its chunkDir
+ *                  file once it is closed.  A recipe digest absent from the index is counted in
+ *                  `missing` (once per occurrence in a recipe) and is no error.  GC frees no arena slot and unloads nothing: the arena
+ *                  stays the ring or retained store that it is, and the bytes of the dropped chunks of
+ *                  a container that keeps others stay in its file.
+ *   Changes        with HDRF_GC_DRY nothing.  Otherwise the index afterwards holds exactly the kept
+ *                  entries, their 11-byte values unchanged; a dropped digest is absent (hdrf_index_get
+ *                  returns 0), and a later write of those bytes stores them as new chunks, exactly as
+ *                  on a DataNode that never saw them.  The index is rebuilt from the kept entries
+ *                  under a new table epoch; any failure before that switch (allocation, a counter
+ *                  check) leaves the index exactly as it was, a failure after it returns
+ *                  HDRF_E_DEVICE / HDRF_E_HIP and marks the context for hdrf_reset. */
+#define HDRF_GC_DRY 1          /* mark and account only; the index is not touched */
+typedef struct {
+    int64_t recipes, recipe_digests;     /* live recipes walked, digests looked up */
+    int64_t entries;                     /* live index entries before the collection */
+    int64_t kept, dropped;               /* entries == kept + dropped */
+    int64_t kept_bytes, dropped_bytes;   /* sum of stop - start over each */
+    int64_t missing;                     /* recipe digests absent from the index (reported, not an error) */
+    int64_t containers, dead_containers; /* containers named by an entry before / with no kept entry */
+} hdrf_gc_stats;
+typedef struct {
+    uint32_t id; int32_t readable;       /* 1: arena-resident or loaded */
+    int64_t kept_chunks, kept_bytes, dropped_chunks, dropped_bytes;
+} hdrf_gc_container;
+/* FsDatasetImpl.invalidate: forget a block. */
+int hdrf_block_delete(hdrf_ctx *ctx, uint64_t block_id);
+int64_t hdrf_gc(hdrf_ctx *ctx, int32_t flags, hdrf_gc_stats *st, hdrf_gc_container *rows, int64_t cap);
+
 /* Device memory helpers for callers without their own allocator (bench, tests). */
 int hdrf_dev_alloc(hdrf_ctx *ctx, uint64_t bytes, void **out);
 int hdrf_dev_free(hdrf_ctx *ctx, void *p);

@@ -185,6 +185,26 @@ public final class HipReductionScheme extends ReductionScheme {
     return scrub0(ctx);
   }
 
+  /**
+   * FsDatasetImpl.invalidate (fsdataset/impl/FsDatasetImpl.java:2026-2100): forget a block.  Its recipe
+   * and length are gone at once; its chunks stay indexed until the next gc().
+   */
+  public void deleteBlock(long blockId) throws IOException {
+    deleteBlock0(ctx, blockId);
+  }
+
+  /**
+   * Index garbage collection: every index entry that no remaining recipe names is dropped, so later
+   * writes of those bytes store them again.  Returns the ids of the closed containers that hold no
+   * kept chunk any more: their chunkDir files may be deleted.
+   */
+  public long[] gc() throws IOException {
+    ByteBuffer ids = ByteBuffer.wrap(gc0(ctx));       // 8 bytes big-endian per id
+    long[] dead = new long[ids.remaining() / 8];
+    ids.asLongBuffer().get(dead);
+    return dead;
+  }
+
   @Override
   public long length(long blockId) throws IOException {
     return length0(ctx, blockId);
@@ -206,6 +226,8 @@ public final class HipReductionScheme extends ReductionScheme {
   private static native byte[] reconstructVerified0(long ctx, long blockId) throws IOException;
   private static native byte[] readRange0(long ctx, long blockId, long offset, long length) throws IOException;
   private static native long scrub0(long ctx) throws IOException;
+  private static native void deleteBlock0(long ctx, long blockId) throws IOException;
+  private static native byte[] gc0(long ctx) throws IOException;
   private static native void reduce0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void submit0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void wait0(long ctx) throws IOException;

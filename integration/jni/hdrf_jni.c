@@ -328,6 +328,51 @@ JNIEXPORT jlong JNICALL JFN(scrub0)(JNIEnv *env, jclass cls, jlong h)
     return (jlong)n;
 }
 
+/* FsDatasetImpl.invalidate (DN/fsdataset/impl/FsDatasetImpl.java:2026-2100): forget a block
+ * (hdrf_block_delete).  Its chunks stay indexed until the next gc0. */
+JNIEXPORT void JNICALL JFN(deleteBlock0)(JNIEnv *env, jclass cls, jlong h, jlong id)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int rc = hdrf_block_delete(ctx, (uint64_t)id);
+    if (rc) throw_io(env, ctx, rc);
+}
+
+/* Index garbage collection (hdrf_gc): every index entry no remaining recipe names is dropped.  Returns
+ * the ids of the dead CLOSED containers (no kept entry; the caller may delete chunkDir + id), 8 bytes
+ * big-endian each: HipReductionScheme.gc() turns them into its long[].  An open container is always
+ * arena-resident, so a dead container that is not resident any more was closed. */
+JNIEXPORT jbyteArray JNICALL JFN(gc0)(JNIEnv *env, jclass cls, jlong h)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int64_t n = hdrf_gc(ctx, HDRF_GC_DRY, NULL, NULL, 0);      /* a dry run sizes the rows */
+    if (n < 0) { throw_io(env, ctx, (int)n); return NULL; }
+    const int64_t cap = n + 1024;                     /* (blocks written in between may add containers) */
+    hdrf_gc_container *rows = (hdrf_gc_container *)malloc((size_t)cap * sizeof *rows);
+    if (!rows) { throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+    n = hdrf_gc(ctx, 0, NULL, rows, cap);
+    if (n < 0 || n > cap) { free(rows); throw_io(env, ctx, n < 0 ? (int)n : HDRF_E_CAPACITY); return NULL; }
+    uint8_t *ids = (uint8_t *)malloc((size_t)(n ? n : 1) * 8);
+    if (!ids) { free(rows); throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+    jsize dead = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (rows[i].kept_chunks) continue;
+        int32_t closed = 0;
+        int64_t r = hdrf_container_read(ctx, rows[i].id, NULL, 0, &closed);
+        if (r == HDRF_E_NOTFOUND) closed = 1;
+        else if (r < 0) { free(ids); free(rows); throw_io(env, ctx, (int)r); return NULL; }
+        if (!closed) continue;
+        for (int b = 0; b < 8; b++) ids[(size_t)dead * 8 + b] = b < 4 ? 0 : (uint8_t)(rows[i].id >> (8 * (7 - b)));
+        dead++;
+    }
+    jbyteArray out = (*env)->NewByteArray(env, dead * 8);
+    if (out) (*env)->SetByteArrayRegion(env, out, 0, dead * 8, (const jbyte *)ids);
+    free(ids);
+    free(rows);
+    return out;
+}
+
 /* stream mode (compressor 0 SnappyCodec / 3 LzopCodec / 4 Lz4Codec / 5 GzipCodec): the block's chunkDir
  * file for packet writes.  LzopCodec headers carry the wall clock, as LzopOutputStream writes
  * System.currentTimeMillis() / 1000. */
