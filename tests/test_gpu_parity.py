@@ -61,7 +61,7 @@ def test_more_boundaries_than_stitch_nodes(kind):
 @pytest.mark.parametrize("hasher", [0, 1])
 def test_long_chunk_sha_lanes(hasher):
     """Chunks >= 64 KiB (the config-4 corpus's text segments hold forced 1,000,000-B cuts) are
-    hashed on sha_full's dedicated long lanes once a completed batch has shown them (sha.hip): the
+    hashed on sha_chunk's dedicated long lanes once a completed batch has shown them (sha.hip): the
     first blocks run without them, the later ones with them, all bit-exact."""
     roots = corpus_roots(3, 0, 1, 24)
     mixed = corpus_block_host(3, roots, 0, 24, 1 << 20, mixed=True)
