@@ -693,7 +693,11 @@ __global__ void __launch_bounds__(64) lz4_decode_kernel(const LzDec *__restrict_
         op += lit;
         if (ip == iend) break;                           // the last sequence has literals only
         if (ip + 2 > iend) { bad = true; break; }
-        const int64_t off = (int64_t)byte(ip) | ((int64_t)byte(ip + 1) << 8);
+        // one statement per byte, low byte first: a refill at ip + 1 must not move the window base
+        // past ip before ip is read (the operand order of | is unspecified)
+        const int64_t off_lo = byte(ip);
+        const int64_t off_hi = byte(ip + 1);
+        const int64_t off = off_lo | (off_hi << 8);
         ip += 2;
         int64_t ml = token & 15;
         if (ml == 15) {

@@ -320,13 +320,20 @@ __global__ void __launch_bounds__(64) sn_decode_kernel(const LzDec *__restrict__
         } else if ((tag & 3) == 2) {
             if (ip + 2 > iend) { bad = true; break; }
             len = (tag >> 2) + 1;
-            off = (int64_t)byte(ip) | ((int64_t)byte(ip + 1) << 8);
+            off = 0;                                     // one statement per byte, low byte first: a
+            for (int k = 0; k < 2; k++) {                // refill must not move the window base past a
+                const int64_t b = byte(ip + k);          // byte not read yet (operand order of |)
+                off |= b << (8 * k);
+            }
             ip += 2;
         } else {
             if (ip + 4 > iend) { bad = true; break; }
             len = (tag >> 2) + 1;
-            off = (int64_t)byte(ip) | ((int64_t)byte(ip + 1) << 8) | ((int64_t)byte(ip + 2) << 16) |
-                  ((int64_t)byte(ip + 3) << 24);
+            off = 0;
+            for (int k = 0; k < 4; k++) {
+                const int64_t b = byte(ip + k);
+                off |= b << (8 * k);
+            }
             ip += 4;
         }
         if (off == 0 || off > op || op + len > oend) { bad = true; break; }
