@@ -2,7 +2,7 @@
 // units share.  Internal: included only by the api*.hip files (api.hip core and batch pipeline,
 // api_rx.hip packet receive, api_stream.hip stream codecs, api_gx.hip node-global phases,
 // api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub, api_gc.hip block deletion and
-// index garbage collection); each of them names in its header comment
+// index garbage collection, api_compact.hip container compaction); each of them names in its header comment
 // the context state it may write.  Everything here but hdrf_ctx itself lives in hdrf::host, hidden
 // from the library's dynamic symbols.
 #pragma once

@@ -316,6 +316,25 @@ hipError_t launch_gc_mark(int hasher, const GcJob *jobs, uint32_t nj, uint64_t t
 hipError_t launch_gc_sweep(int hasher, const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *mark,
                            const uint32_t *cids, int ncont, GcContCount *cc, uint32_t *seen, uint32_t *dw_rows,
                            uint8_t *val_rows, uint64_t row_cap, uint32_t *wg, GcCounters *C, int wgs, hipStream_t st);
+// container compaction (compact.hip; rows, counters and the scratch layout are compact_plan.hpp's).
+struct CpRow;
+struct CpList;
+struct CpCount;
+// collect: one lane per table slot; the live entries of the list's containers.  rows == nullptr: the
+// first run, which fills cc[] (zeroed by the caller) and wg[] (the rows each workgroup will write);
+// otherwise the second run, with the same wgs, which writes the rows (row_cap of them at most).
+hipError_t launch_cp_collect(const IndexEntry *tab, int log2cap, unsigned long long key, const CpList &list, CpCount *cc,
+                             uint32_t *wg, CpRow *rows, uint64_t row_cap, uint32_t *err, int wgs, hipStream_t st);
+// cover: the rows' bits into the maps (cleared by the caller; map_words words per container), the
+// prefix arrays, cc[].covered and cc[].moved
+hipError_t launch_cp_cover(const CpRow *rows, uint32_t nrows, const CpList &list, uint32_t *maps, uint32_t *pres,
+                           uint64_t map_words, CpCount *cc, hipStream_t st);
+// gather the rows of the containers in the bit mask `go` into their images (img + j * img_stride)
+hipError_t launch_cp_gather(const CpRow *rows, uint32_t nrows, uint32_t go, const uint64_t *bases, const uint32_t *maps,
+                            const uint32_t *pres, uint64_t map_words, uint8_t *img, uint64_t img_stride, hipStream_t st);
+// the new start / stop of the entries of the containers in `go`
+hipError_t launch_cp_rewrite(const CpRow *rows, uint32_t nrows, uint32_t go, const uint32_t *maps, const uint32_t *pres,
+                             uint64_t map_words, IndexEntry *tab, hipStream_t st);
 hipError_t launch_corpus(uint8_t *dev, const uint32_t *d_roots, int64_t nblocks, int64_t spb, int64_t seg_bytes,
                          uint64_t seed, int mixed, hipStream_t st);
 

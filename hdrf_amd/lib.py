@@ -39,12 +39,15 @@ EXPORTS = [
     "hdrf_scrub", "hdrf_reconstruct_verified", "hdrf_reconstruct_block_verified",
     "hdrf_read_batch", "hdrf_read_range",
     "hdrf_block_delete", "hdrf_gc",
+    "hdrf_compact",
 ]
 
 ALLOC_STATE_BYTES = 128     # HDRF_ALLOC_STATE_BYTES
 PIPELINE_DEPTH = 5          # HDRF_PIPELINE_DEPTH: batches in flight
 READ_MAX_REQS = 256         # HDRF_READ_MAX_REQS: requests of one hdrf_read_batch call
 GC_DRY = 1                  # HDRF_GC_DRY: mark and account only
+COMPACT_MAX = 16            # HDRF_COMPACT_MAX: containers of one hdrf_compact call
+COMPACT_DRY = 1             # HDRF_COMPACT_DRY: account only
 
 
 # per-stage timers of hdrf_stage_times (kernel names in parentheses)
@@ -112,6 +115,12 @@ class GcStats(ctypes.Structure):            # hdrf_gc_stats (80 B)
 class GcContainer(ctypes.Structure):        # hdrf_gc_container (40 B)
     _fields_ = [("id", ctypes.c_uint32), ("readable", ctypes.c_int32), ("kept_chunks", ctypes.c_int64),
                 ("kept_bytes", ctypes.c_int64), ("dropped_chunks", ctypes.c_int64), ("dropped_bytes", ctypes.c_int64)]
+
+
+class CompactRow(ctypes.Structure):         # hdrf_compact_row (56 B)
+    _fields_ = [("id", ctypes.c_uint32), ("status", ctypes.c_int32), ("chunks", ctypes.c_int64),
+                ("moved_chunks", ctypes.c_int64), ("old_bytes", ctypes.c_int64), ("new_bytes", ctypes.c_int64),
+                ("file_bytes", ctypes.c_int64), ("data_off", ctypes.c_int64)]
 
 
 class GxLayout(ctypes.Structure):
@@ -206,6 +215,8 @@ def load():
         "hdrf_block_delete": (ctypes.c_int, [_vp, ctypes.c_uint64]),
         "hdrf_gc": (ctypes.c_int64, [_vp, ctypes.c_int32, ctypes.POINTER(GcStats), ctypes.POINTER(GcContainer),
                                      ctypes.c_int64]),
+        "hdrf_compact": (ctypes.c_int64, [_vp, ctypes.c_int32, _u32p, ctypes.c_int32, ctypes.POINTER(CompactRow), _u8p,
+                                          ctypes.c_int64, _i64p]),
         "hdrf_gx_read_locate": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp]),
         "hdrf_gx_flush_fn": (ctypes.c_int64, [_vp, _vp, ctypes.c_int64]),
         "hdrf_gx_alloc_scan": (ctypes.c_int32, [_vp, _vp, _vp, _u8p, _u8p]),
@@ -694,6 +705,35 @@ class Context:
             stats = {f: getattr(st, f) for f, _ in GcStats._fields_}
             rows = [{f: getattr(r, f) for f, _ in GcContainer._fields_} for r in buf[:min(n, cap)]]
             return stats, rows
+
+    def compact(self, ids, dry=False, want_files=True):
+        """hdrf_compact: rewrite the closed containers `ids` (COMPACT_MAX at most) so that only the chunks
+        live index entries name remain, packed to the front in their old order.  Returns (rows, files):
+        rows = one dict(id, status, chunks, moved_chunks, old_bytes, new_bytes, file_bytes, data_off) per id,
+        in the order given (status 0 compacted, 1 nothing to reclaim, 2 dead, < 0 an HDRF_E_* code: not
+        eligible or inconsistent); files = {id: the new chunkDir file} for the status-0 rows (empty with
+        dry=True or want_files=False).  Raises HdrfError only on a call-level failure."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        n = int(a.size)
+        rows = (CompactRow * max(n, 1))()
+        need = ctypes.c_int64(0)
+        give = want_files and not dry
+        cap = int(self.cfg.container_max) if give and n else 0      # a first guess: `need` corrects it
+        while True:
+            buf = np.zeros(max(cap, 1), np.uint8) if give else None
+            rc = self.L.hdrf_compact(self._h, COMPACT_DRY if dry else 0, _p(a if n else np.zeros(1, np.uint32), _u32p), n,
+                                     rows, _p(buf) if give else None, cap, ctypes.byref(need))
+            if rc == -4 and give and need.value > cap:        # HDRF_E_CAPACITY: nothing changed, grow and call again
+                cap = int(need.value)
+                continue
+            self._ck(rc)
+            out = [{f: getattr(r, f) for f, _ in CompactRow._fields_} for r in rows[:n]]
+            files = {}
+            if give:
+                for r in out:
+                    if r["status"] == 0 and r["data_off"] >= 0:
+                        files[r["id"]] = buf[r["data_off"]:r["data_off"] + r["file_bytes"]].tobytes()
+            return out, files
 
     def container(self, cid):
         closed = ctypes.c_int32(0)

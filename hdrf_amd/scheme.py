@@ -70,6 +70,11 @@ class HipReductionScheme(ReductionScheme):
         """Drop every index entry no remaining recipe names: (stats, per-container rows)."""
         return self.ctx.gc(dry=dry)
 
+    def compact(self, ids, dry=False, want_files=True):
+        """Rewrite closed containers so that only the chunks the index still names remain:
+        (per-container rows, {container id: its new chunkDir file})."""
+        return self.ctx.compact(ids, dry=dry, want_files=want_files)
+
     def recipe(self, block_id):
         return self.ctx.recipe(block_id)
 

@@ -423,6 +423,64 @@ typedef struct {
 int hdrf_block_delete(hdrf_ctx *ctx, uint64_t block_id);
 int64_t hdrf_gc(hdrf_ctx *ctx, int32_t flags, hdrf_gc_stats *st, hdrf_gc_container *rows, int64_t cap);
 
+/* Container compaction: give back the bytes of dropped chunks.  hdrf_gc drops index entries and
+ * reports, per container, the bytes nobody names any more (dropped_bytes); a container's chunkDir file
+ * can only be deleted when nothing in it is kept.  hdrf_compact rewrites the closed containers the
+ * caller names so that only the chunks live index entries name remain, packed to the front in their
+ * old order: sort the container's live entries by start; chunk k's new start is the sum of the lengths
+ * of chunks 0..k-1, its new stop is start + length, its bytes are copied unchanged.
+ *   When it runs   it takes the context lock and completes the batches in flight, like the other views.
+ *                  Single-node contexts (HDRF_E_UNSUPPORTED when n_ranks > 1).  It needs no recipes:
+ *                  live means "a live index entry of the current epoch names it", so the intended
+ *                  sequence is hdrf_block_delete ... hdrf_gc ... hdrf_compact.
+ *   Returns        the number of rows with status 0, or a call-level failure that changes nothing:
+ *                  HDRF_E_INVAL (null context, n outside [0, HDRF_COMPACT_MAX], n > 0 without ids or
+ *                  rows, a duplicate id, unknown flags), HDRF_E_NOMEM (the staging: container_max
+ *                  bytes per container), HDRF_E_CAPACITY (out is given and the files of the status-0
+ *                  rows do not fit in out_cap; *need is their total).  rows[i] answers ids[i], and one
+ *                  failing row does not stop the others: HDRF_E_NOTFOUND (neither arena-resident nor
+ *                  loaded), HDRF_E_INVAL (open, or with retain_containers closed and not yet drained:
+ *                  hdrf_drain_containers first), HDRF_E_DEVICE (the live ranges that name it overlap,
+ *                  or one is empty or reaches past the container's bytes), 2 (no live entry names it:
+ *                  the DataNode deletes the file), 1 (the live ranges already tile the container),
+ *                  0 (compacted).  A container whose status is not 0 is left exactly as it was; its row
+ *                  has moved_chunks 0, file_bytes 0, data_off -1, and new_bytes = old_bytes (status 1
+ *                  or HDRF_E_DEVICE) or 0 (status 2); a row the host maps refuse is all zeros but id,
+ *                  status and data_off.
+ *   Changes        with HDRF_COMPACT_DRY nothing.  Otherwise, for the status-0 rows: exactly the index
+ *                  entries that name the container get their new start / stop, every other field and
+ *                  every other entry stays bit-identical (no new epoch, no rebuild).  A loaded
+ *                  container's device copy, or an arena-resident container's arena slot (and under
+ *                  compressor 2 its Lz4Codec file in the compressed arena), becomes the new image; if
+ *                  an id is both, the resident copy is compacted and the loaded one is freed.
+ *                  hdrf_stats.closed_raw_bytes / closed_file_bytes go down by the differences for
+ *                  arena-resident containers.  The allocator, the open containers, recipes and the
+ *                  drain bookkeeping are untouched.  All or nothing: everything is classified, checked,
+ *                  gathered and compressed in a staging area first, and only then committed; a failure
+ *                  before the commit leaves the context as it was, a HIP failure during it marks the
+ *                  context lost (HDRF_E_HIP until hdrf_reset), as hdrf_gc's rebuild does.
+ * The file handed out, out[data_off, data_off + file_bytes), is the whole new chunkDir + id file: the
+ * raw image, or under compressor 2 the Lz4Codec file of the image exactly as the storer's close writes
+ * it.  With out == NULL the compaction still happens and data_off is -1; an arena-resident file can then
+ * be read with hdrf_container_read.  The new index values become durable with the caller's next
+ * hdrf_index_dump, as after hdrf_gc: the DataNode replaces the files and the dump together. */
+#define HDRF_COMPACT_MAX 16    /* containers per call (the staging is container_max bytes each) */
+#define HDRF_COMPACT_DRY 1     /* account only: no byte, entry or host record changes */
+typedef struct {
+    uint32_t id;
+    int32_t  status;        /* 0 compacted (DRY: would be); 1 nothing to reclaim; 2 dead: no live entry names it;
+                               < 0: HDRF_E_* — not eligible or inconsistent.  Anything but 0: left exactly as it was */
+    int64_t  chunks;        /* live index entries that name the container */
+    int64_t  moved_chunks;  /* of those, entries whose start changes */
+    int64_t  old_bytes;     /* raw length before */
+    int64_t  new_bytes;     /* raw length after == sum of stop - start over `chunks` */
+    int64_t  file_bytes;    /* new chunkDir file: new_bytes, or the Lz4Codec file's length under compressor 2;
+                               DRY under compressor 2: -1 (not computed) */
+    int64_t  data_off;      /* the file is out[data_off, data_off + file_bytes); -1 when not handed out */
+} hdrf_compact_row;
+int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *ids, int32_t n, hdrf_compact_row *rows, uint8_t *out,
+                     int64_t out_cap, int64_t *need);
+
 /* Device memory helpers for callers without their own allocator (bench, tests). */
 int hdrf_dev_alloc(hdrf_ctx *ctx, uint64_t bytes, void **out);
 int hdrf_dev_free(hdrf_ctx *ctx, void *p);

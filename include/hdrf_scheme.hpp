@@ -147,6 +147,34 @@ class HipReductionScheme final : public ReductionScheme {
         }
     }
 
+    // rewrite the closed containers `ids` (HDRF_COMPACT_MAX at most) so that only the chunks live index
+    // entries name remain: one row per id, and in files (when given) the new chunkDir file of every
+    // status-0 row, in the rows' order.  dry: account only.
+    std::vector<hdrf_compact_row> compact(const std::vector<uint32_t> &ids, std::vector<std::vector<uint8_t>> *files = nullptr,
+                                          bool dry = false)
+    {
+        std::vector<hdrf_compact_row> rows(ids.size());
+        std::vector<uint8_t> buf(files && !dry ? 1 : 0);              // (a null buffer would mean: no files wanted)
+        for (;;) {
+            int64_t need = 0;
+            const int64_t n = hdrf_compact(ctx_, dry ? HDRF_COMPACT_DRY : 0, ids.data(), (int32_t)ids.size(), rows.data(),
+                                           buf.empty() ? nullptr : buf.data(), (int64_t)buf.size(), &need);
+            if (n == HDRF_E_CAPACITY && need > (int64_t)buf.size()) {       // nothing changed: grow, call again
+                buf.resize((size_t)need);
+                continue;
+            }
+            if (n < 0) check((int)n);
+            break;
+        }
+        if (files) {
+            files->clear();
+            for (const hdrf_compact_row &r : rows)
+                if (r.status == 0 && r.data_off >= 0)
+                    files->emplace_back(buf.begin() + r.data_off, buf.begin() + r.data_off + r.file_bytes);
+        }
+        return rows;
+    }
+
     int64_t length(uint64_t block_id) override
     {
         int64_t n = hdrf_block_length(ctx_, block_id);

@@ -205,6 +205,19 @@ public final class HipReductionScheme extends ReductionScheme {
     return dead;
   }
 
+  /**
+   * Container compaction: the closed containers ids (16 at most per call) are rewritten so that only
+   * the chunks the index still names remain, and the new files replace chunkDir + id.  Returns the ids
+   * that were compacted; the others had nothing to reclaim, were dead (gc() names those) or not
+   * eligible.  Drain first (drainContainers) and persist the index afterwards.
+   */
+  public long[] compact(String chunkDir, long[] ids) throws IOException {
+    ByteBuffer out = ByteBuffer.wrap(compact0(ctx, chunkDir, ids));   // 8 bytes big-endian per id
+    long[] done = new long[out.remaining() / 8];
+    out.asLongBuffer().get(done);
+    return done;
+  }
+
   @Override
   public long length(long blockId) throws IOException {
     return length0(ctx, blockId);
@@ -228,6 +241,7 @@ public final class HipReductionScheme extends ReductionScheme {
   private static native long scrub0(long ctx) throws IOException;
   private static native void deleteBlock0(long ctx, long blockId) throws IOException;
   private static native byte[] gc0(long ctx) throws IOException;
+  private static native byte[] compact0(long ctx, String chunkDir, long[] ids) throws IOException;
   private static native void reduce0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void submit0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void wait0(long ctx) throws IOException;

@@ -373,6 +373,58 @@ JNIEXPORT jbyteArray JNICALL JFN(gc0)(JNIEnv *env, jclass cls, jlong h)
     return out;
 }
 
+/* Container compaction (hdrf_compact): the closed containers `ids` (HDRF_COMPACT_MAX at most) are
+ * rewritten so that only the chunks the index still names remain; the new file of every compacted
+ * container replaces chunkDir + id (written beside it, then renamed over it).  Returns the ids that
+ * were compacted, 8 bytes big-endian each, as gc0 does.  The new index values are durable with the
+ * caller's next index dump; a crash between the rename and that dump is the DataNode's to handle. */
+JNIEXPORT jbyteArray JNICALL JFN(compact0)(JNIEnv *env, jclass cls, jlong h, jstring chunkDir, jlongArray jids)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    const jsize n = (*env)->GetArrayLength(env, jids);
+    if (n < 0 || n > HDRF_COMPACT_MAX) { throw_io(env, ctx, HDRF_E_INVAL); return NULL; }
+    uint32_t ids[HDRF_COMPACT_MAX];
+    hdrf_compact_row rows[HDRF_COMPACT_MAX];
+    jlong *w = (*env)->GetLongArrayElements(env, jids, NULL);
+    if (!w && n) { throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+    for (jsize i = 0; i < n; i++) ids[i] = (uint32_t)w[i];
+    if (w) (*env)->ReleaseLongArrayElements(env, jids, w, JNI_ABORT);
+    int64_t cap = 1, need = 0, got;
+    uint8_t *buf = (uint8_t *)malloc((size_t)cap);
+    for (;;) {
+        if (!buf) { throw_io(env, ctx, HDRF_E_NOMEM); return NULL; }
+        got = hdrf_compact(ctx, 0, ids, (int32_t)n, rows, buf, cap, &need);
+        if (got != HDRF_E_CAPACITY || need <= cap) break;  /* HDRF_E_CAPACITY changed nothing: grow, call again */
+        free(buf);
+        cap = need;
+        buf = (uint8_t *)malloc((size_t)cap);
+    }
+    if (got < 0) { free(buf); throw_io(env, ctx, (int)got); return NULL; }
+    const char *dir = (*env)->GetStringUTFChars(env, chunkDir, NULL);
+    uint8_t out[HDRF_COMPACT_MAX * 8];
+    jsize done = 0;
+    int rc = 0;
+    for (jsize i = 0; i < n && !rc; i++) {
+        if (rows[i].status != 0) continue;
+        char path[4096], tmp[4200];
+        snprintf(path, sizeof path, "%s%u", dir, rows[i].id);
+        snprintf(tmp, sizeof tmp, "%s.compact", path);
+        FILE *f = fopen(tmp, "wb");
+        int ok = f && fwrite(buf + rows[i].data_off, 1, (size_t)rows[i].file_bytes, f) == (size_t)rows[i].file_bytes;
+        if (f) ok = (fclose(f) == 0) && ok;
+        if (!ok || rename(tmp, path) != 0) { rc = HDRF_E_INVAL; break; }
+        for (int b = 0; b < 8; b++) out[(size_t)done * 8 + b] = b < 4 ? 0 : (uint8_t)(rows[i].id >> (8 * (7 - b)));
+        done++;
+    }
+    (*env)->ReleaseStringUTFChars(env, chunkDir, dir);
+    free(buf);
+    if (rc) { throw_io(env, ctx, rc); return NULL; }
+    jbyteArray r = (*env)->NewByteArray(env, done * 8);
+    if (r) (*env)->SetByteArrayRegion(env, r, 0, done * 8, (const jbyte *)out);
+    return r;
+}
+
 /* stream mode (compressor 0 SnappyCodec / 3 LzopCodec / 4 Lz4Codec / 5 GzipCodec): the block's chunkDir
  * file for packet writes.  LzopCodec headers carry the wall clock, as LzopOutputStream writes
  * System.currentTimeMillis() / 1000. */
