@@ -1143,6 +1143,28 @@ extern "C" int hdrf_batch_placement(hdrf_ctx *ctx, int32_t b, uint32_t *cid, uin
     return 0;
 }
 
+// Test hook: the chunker's per-segment records of block b, as the batch's kernels left them in the
+// slot (d_meta is written by the lane walk, the repair and the stitch of the slot's own batch only,
+// and the next submit to the slot waits for this batch first: the same window as d_off above).
+extern "C" int hdrf_batch_seg_trace(hdrf_ctx *ctx, int32_t b, hdrf_seg_trace *out, int64_t cap, int32_t *rq_count)
+{
+    HDRF_LOCK(ctx);
+    if (int rc = check_b(ctx, b)) return rc;
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "segment trace on node-global contexts");
+    if (!out) return set_err(ctx, HDRF_E_INVAL, "null trace buffer");
+    const Slot &R = ctx->sl[ctx->res];
+    const BlockDesc &d = R.h_desc[b];
+    if (cap < d.nseg) return set_err(ctx, HDRF_E_CAPACITY, "segment trace capacity");
+    std::vector<SegMeta> m((size_t)d.nseg);
+    HIPCK(hipMemcpy(m.data(), R.d_meta + d.seg0, sizeof(SegMeta) * m.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < d.nseg; k++) {
+        const SegMeta &s = m[(size_t)k];
+        out[k] = hdrf_seg_trace{s.n_main, s.n_over, s.sync, s.jmp, s.jj, s.n_ext, s.ext_dst, s.pad[0]};
+    }
+    if (rq_count) HIPCK(hipMemcpy(rq_count, R.d_rq_count, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return d.nseg;
+}
+
 extern "C" int hdrf_reduce_block(hdrf_ctx *ctx, uint64_t block_id, const uint8_t *data, uint64_t len,
                                  hdrf_block_result *out)
 {

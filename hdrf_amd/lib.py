@@ -40,6 +40,7 @@ EXPORTS = [
     "hdrf_read_batch", "hdrf_read_range",
     "hdrf_block_delete", "hdrf_gc",
     "hdrf_compact",
+    "hdrf_batch_seg_trace",
 ]
 
 ALLOC_STATE_BYTES = 128     # HDRF_ALLOC_STATE_BYTES
@@ -224,6 +225,8 @@ def load():
         "hdrf_batch_info": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _i64p]),
         "hdrf_batch_offsets": (ctypes.c_int, [_vp, ctypes.c_int32, _u32p, ctypes.c_int64]),
         "hdrf_batch_digests": (ctypes.c_int, [_vp, ctypes.c_int32, _u8p, ctypes.c_int64]),
+        "hdrf_batch_seg_trace": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                ctypes.POINTER(ctypes.c_int32)]),
         "hdrf_batch_is_new": (ctypes.c_int, [_vp, ctypes.c_int32, _u8p, ctypes.c_int64]),
         "hdrf_batch_placement": (ctypes.c_int, [_vp, ctypes.c_int32, _u32p, _u32p, ctypes.c_int64]),
         "hdrf_index_get": (ctypes.c_int, [_vp, _u8p, _u8p]),
@@ -564,6 +567,17 @@ class Context:
         self._ck(self.L.hdrf_batch_placement(self._h, b, _p(cid, _u32p), _p(pos, _u32p), n))
         return {"offsets": offs[:n], "digests": digs[:n * self.H].reshape(n, self.H), "is_new": isnew[:n],
                 "container_id": cid[:n], "container_pos": pos[:n], "store_size": ss}
+
+    SEG_TRACE_FIELDS = ("n_main", "n_over", "sync", "jmp", "jj", "n_ext", "ext_dst", "n_piece")
+
+    def batch_seg_trace(self, b, nseg_cap):
+        """Test hook (hdrf_batch_seg_trace): -> ({field: int32 array, one entry per lane-walk segment of
+        block b of the last completed batch}, the batch's repair-queue count).  nseg_cap: at least the
+        block's segment count."""
+        out = np.zeros((max(int(nseg_cap), 1), len(self.SEG_TRACE_FIELDS)), np.int32)
+        rq = ctypes.c_int32()
+        n = self._ck(self.L.hdrf_batch_seg_trace(self._h, b, out.ctypes.data_as(_vp), out.shape[0], ctypes.byref(rq)))
+        return {f: out[:n, i].copy() for i, f in enumerate(self.SEG_TRACE_FIELDS)}, rq.value
 
     # ---- Redis / chunkDir views ---------------------------------------------------------
     def index_get(self, digest):

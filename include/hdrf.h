@@ -213,6 +213,24 @@ int hdrf_batch_offsets(hdrf_ctx *ctx, int32_t b, uint32_t *out, int64_t cap);
 int hdrf_batch_digests(hdrf_ctx *ctx, int32_t b, uint8_t *out, int64_t cap_bytes);
 int hdrf_batch_is_new(hdrf_ctx *ctx, int32_t b, uint8_t *out, int64_t cap);
 int hdrf_batch_placement(hdrf_ctx *ctx, int32_t b, uint32_t *cid, uint32_t *pos, int64_t cap);
+/* Test hook (in the spirit of debug_tag_bits): which way the chunker's bookkeeping went for block b of
+ * the batch hdrf_batch_* report.  One record per lane-walk segment of the block, in order: the
+ * speculative walk's main / overrun cut counts, the boundary's final status (sync >= 0: overrun cut
+ * sync & 0xffff equals the next segment's cut sync >> 16; -1 the chain ran to the block end; -3
+ * repaired: it met segment + jmp at that segment's cut jj after n_ext repair cuts; -4 the repair gave
+ * up), where the repair's cuts went in the block's offsets (ext_dst, -1: the boundary is not on the
+ * block's path) and how many offsets the segment contributed (n_piece, 0 off the path).
+ * *rq_count = the batch's failed speculative boundaries (the repair queue's length), all blocks.
+ * Returns the block's segment count (HDRF_E_CAPACITY when cap is smaller).  Read-only: it copies
+ * what the batch's chunking kernels left in the pipeline slot and launches nothing.  Validity: like
+ * hdrf_batch_offsets, from the hdrf_wait_batch (or hdrf_reduce_*) that completed the batch until the
+ * slot is submitted to again, i.e. until HDRF_PIPELINE_DEPTH - 1 further batches have been submitted;
+ * a submit waits for its slot's previous batch, so nothing in flight writes the slot in between.
+ * Single-GPU contexts only (n_ranks = 1). */
+typedef struct {
+    int32_t n_main, n_over, sync, jmp, jj, n_ext, ext_dst, n_piece;
+} hdrf_seg_trace;
+int hdrf_batch_seg_trace(hdrf_ctx *ctx, int32_t b, hdrf_seg_trace *out, int64_t cap, int32_t *rq_count);
 
 /* Index (Redis) views. GET digest -> 11-byte chunkMeta value (DN/chunkMeta.java:62-77).
  * Returns 1 if found, 0 if absent, <0 on error. */

@@ -445,3 +445,274 @@ def end_blocks():
         chunks = [_rand_chunk(r[j], L) for j, L in enumerate(lens + [last])]
         out.append(designed_block(chunks, 620 + i, tail=tail))
     return out
+
+
+# ---- bookkeeping families: the lane walk's overrun, the repair, the stitch (tests/lane_model.py) ---
+# Blocks whose only non-negative bytes are placed markers.  With equal markers the rule reduces to
+# "the next cut is one past the first marker at or beyond p + 701", so a lattice of markers every d
+# bytes (351 <= d <= 700) carries two disjoint chains, on the even and on the odd markers, and both
+# segment lengths are multiples of d: every segment's speculative chain starts on the even one.
+# Deleting one marker moves the chain that would have cut on it to the next marker, i.e. onto the
+# other chain; a chain already there is not touched.  So:
+#   * deleting the even marker at a segment start S (a + 1) sends segment a's chain onto the odd
+#     markers in its overrun, where the next segment's (even) chain never meets it: the boundary fails
+#     at the overrun cut seg_len or more past the segment end, or at its kLaneOver-th overrun cut;
+#   * deleting an odd marker further on brings it back, onto a cut of the segment that holds it: at
+#     overrun cut i (a sync at (i, i)) or at the repair's cut r (a jump with n_ext = r).
+def marker_ends(n, marks):
+    """End offsets under the rule stated on markers alone ({position: value}; every other byte is
+    negative and the first window holds a marker)."""
+    import bisect
+    pos = sorted(marks)
+    val = [marks[p] for p in pos]
+    ends, p = [], 0
+    while p + W <= n - 1:
+        a, b = bisect.bisect_left(pos, p), bisect.bisect_left(pos, p + W + 1)
+        assert p > 0 or b > a, "the first window needs a marker"
+        m = max([0] + val[a:b])
+        i = b
+        while i < len(pos) and val[i] < m:
+            i += 1
+        if i < len(pos) and pos[i] <= min(p + MAX_L, n - 1):
+            p = pos[i] + 1
+        elif p + MAX_L <= n - 1:
+            p += FORCED
+        else:
+            break
+        ends.append(p)
+    return np.array(ends[:-1] + [n], np.uint32)
+
+
+def marker_block(n, marks, seed):
+    buf = prng_bytes(seed, n) | np.uint8(0x80)
+    pos = np.fromiter(marks.keys(), np.int64, len(marks))
+    buf[pos] = np.fromiter(marks.values(), np.uint8, len(marks))
+    return _frozen(buf), marker_ends(n, marks)
+
+
+def lattice_fail_cuts(seg_len, d, lane_over=8):
+    """overrun cuts a chain on the odd markers records before its boundary fails"""
+    return min(seg_len // d // 2, lane_over - 1) + 1
+
+
+def lattice_episodes(seg_len, d, script, seed, a0=1, tail_segs=2, tail_bytes=1234, lane_over=8):
+    """A lattice block (spacing d) with one scripted event after another on the block's own chain.
+    The chain is on the even markers in segment a; events:
+      ("sync", i)         segment a's chain leaves for the odd markers at its end and is back at overrun
+                          cut i, which is the next segment's cut i: sync (i, i); a += 1
+      ("repair", r)       it leaves and is back at the repair's cut r, a main cut of the segment m
+                          holding it: jump, n_ext = r (r + 1 when cut r is one past a segment start,
+                          an overrun cut of segment m - 1: not matched); a = m
+      ("repair", r, off)  also segments a + b, b in off, leave at their ends: failed boundaries that the
+                          jump passes over
+      ("at", k)           the next event is at segment k (>= a)
+      ("leave",)          it leaves and never returns (the last event)
+    -> (block, end offsets, [(event, segment, target segment or None)])."""
+    S = seg_len // d
+    assert S * d == seg_len and S % 2 == 0 and 351 <= d <= W
+    nf = lattice_fail_cuts(seg_len, d, lane_over)
+    deleted, log, a = set(), [], a0
+    for ev in script:
+        if ev[0] == "at":
+            assert ev[1] >= a
+            a = ev[1]
+        elif ev[0] == "sync":
+            deleted |= {S * (a + 1), S * (a + 1) + 2 * ev[1] + 1}
+            log.append((ev, a, a + 1))
+            a += 1
+        elif ev[0] == "repair":
+            first_odd = S * (a + 1) + 2 * nf - 1          # the failing overrun cut's marker
+            back = first_odd + 2 * ev[1] + 1
+            deleted |= {S * (a + 1), back - 1}
+            for b in (ev[2] if len(ev) > 2 else ()):
+                assert S * (a + b + 1) < back - 2
+                deleted.add(S * (a + b + 1))
+            m = (back + (2 if back % S == 0 else 0)) // S
+            log.append((ev, a, m))
+            a = m
+        else:
+            assert ev[0] == "leave" and ev is script[-1]
+            deleted.add(S * (a + 1))
+            log.append((ev, a, None))
+    n = (a + tail_segs) * seg_len + tail_bytes
+    marks = {d * j: 64 for j in range((n - 1) // d + 1) if j not in deleted}
+    return marker_block(n, marks, seed) + (log,)
+
+
+# n_ext values the issue names (the kept-cuts path's 64 / 65 and the list sink's 64 / 128 edges), and
+# more for jmp in {1, 2, 3, >= 8} and jj in {0, 1, last main cut}; per (seg_len, d): the lattice gives
+# a cut r a main-cut landing unless (first landing + 2 r) % S == 0
+REPAIR_N_EXT = (2, 3, 63, 64, 65, 66, 128, 129, 130)
+REPAIR_SCRIPTS = {
+    (2808, 351): (1, 2, 4, 64, 65, 66, 128, 129, 130),    # r % 4 == 3 lands one past a segment start
+    (2808, 468): (3, 63),
+    (14040, 351): (1, 2, 3, 11, 13, 14, 20, 40, 63, 64, 65, 66, 128, 129, 130, 160),
+}
+
+
+@functools.lru_cache(None)
+def repair_sweep(seg_len, d, hole=False):
+    """(B) on-path repairs with the n_ext of REPAIR_SCRIPTS, back to back, the first at segment 62 (the
+    first wave's last lane, which reads the helper lane's list; hole: at segment 63, the next wave's
+    lane 0); the repairs of n_ext >= 64 pass over two failed boundaries, the first next to the on-path
+    one.  hole: every repair comes back one past a segment start instead, an overrun cut of the
+    segment before (met, not matched) and is matched one cut on."""
+    rs = REPAIR_SCRIPTS[(seg_len, d)]
+    S = seg_len // d
+    script = [("at", 63 if hole else 62)]
+    for r in rs:
+        if hole:
+            r = next(x for x in range(r, r + S) if (2 * lattice_fail_cuts(seg_len, d) + 2 * x) % S == 0)
+        script.append(("repair", r, (1, 2)) if r >= 64 else ("repair", r))
+    return lattice_episodes(seg_len, d, script, 700 + d + (1 if hole else 0))
+
+
+@functools.lru_cache(None)
+def overrun_sweep(seg_len):
+    """(A) syncs at overrun cut number 1, 2, ... (every one the segment length leaves room for, up to
+    kLaneOver = 8), at lanes 62 and 63 of the first wave among others; then a chain that leaves for
+    good two segments before the block end."""
+    idx = [i for i in (0, 1, 2, 6, 7) if 2 * i + 2 < seg_len // 351]    # the shared cut lies inside the next segment
+    script = [("sync", i) for i in idx] + [("at", 62), ("sync", 0), ("sync", 1), ("at", 70)] + \
+             [("sync", i) for i in idx] + [("leave",)]
+    return lattice_episodes(seg_len, 351, script, 720 + seg_len % 97, tail_segs=2, tail_bytes=900)
+
+
+@functools.lru_cache(None)
+def small_blocks(seg_len):
+    """(A) blocks of exactly 1 and 2 segments, and 2 segments plus one byte."""
+    out = []
+    for i, n in enumerate((seg_len, 2 * seg_len, 2 * seg_len + 1)):
+        marks = {351 * j: 64 for j in range((n - 1) // 351 + 1) if j != seg_len // 351}
+        out.append(marker_block(n, marks, 730 + i))
+    return out
+
+
+def _background(lo, hi, step=936, phase=467):
+    """markers of one chain (spacing >= 702) at step * j + phase within [lo, hi)"""
+    j0 = -(-(lo - phase) // step)
+    return {step * j + phase: 64 for j in range(max(j0, 0), (hi - phase + step - 1) // step) if step * j + phase < hi}
+
+
+def _edge_start(seg_len, a_min, back, capped):
+    """-> (a, P): a segment a >= a_min and a cut P in it, more than 701 B before its end, from which the
+    search for the byte target - 1, target = (a + 2) * seg_len - back, reads a last 1-KiB view (views
+    start at P & ~63) that begins within 16 B beyond over_lim = (a + 2) * seg_len - 64 (capped: the search
+    is given up) / within 16 B at or before it (it is not)."""
+    for a in range(a_min, a_min + 8):
+        over_lim, target = (a + 2) * seg_len - 64, (a + 2) * seg_len - back
+        for P in range((a + 1) * seg_len - 720, a * seg_len + 800, -1):
+            b0 = P & ~63
+            vs = b0 + 1024 * ((target - 1 - b0) // 1024)
+            if (0 < vs - over_lim <= 16) if capped else (0 <= over_lim - vs < 16):
+                return a, P
+    raise AssertionError("no such start")
+
+
+EDGE_KINDS = ("last_byte", "last_byte_capped", "one_past", "at_over_lim", "below_over_lim")
+
+
+@functools.lru_cache(None)
+def overrun_edges(seg_len):
+    """(A) one chain (markers >= 702 B apart), and at five boundaries a (e = the next segment's start)
+    one long chunk from a cut P in segment a:
+      last_byte         to the cut e + seg_len - 1, the next segment's first cut: sync (0, 0); the search's
+                        last view begins less than 16 B before over_lim
+      last_byte_capped  the same cut from a P whose search would read a view that begins at most 16 B
+                        beyond over_lim: fails
+                        with no overrun cut, and the repair's first cut is shared (n_ext 1, jmp 1)
+      one_past          to the cut e + seg_len exactly: fails, although it is the next segment's cut
+      at_over_lim       a cut at over_lim that the next segment's chain passes over (a 100-valued
+                        marker inside the window of its 64-valued cut): fails there, one overrun cut
+      below_over_lim    the same one byte earlier: goes on, and fails at its next cut (two)
+    -> (block, end offsets, {kind: segment a})."""
+    marks, where = {}, {}
+    a, lo = 3, 0
+    for kind in EDGE_KINDS:
+        if kind in ("last_byte", "last_byte_capped", "one_past"):
+            a, P = _edge_start(seg_len, a, 0 if kind == "one_past" else 1, kind == "last_byte_capped")
+            c = (a + 2) * seg_len - (0 if kind == "one_past" else 1)
+            marks.update(_background(lo, P - 702))
+            marks[P - 1] = 64
+            marks[c - 1] = 64
+            lo = c - 1 + 702
+        else:
+            e = (a + 1) * seg_len
+            c = e + seg_len - 64 - (1 if kind == "below_over_lim" else 0)
+            P = e - 300
+            marks.update(_background(lo, P - 702))
+            marks[P - 1] = 64
+            marks[P + 5] = 100                       # P's window: its chain passes every 64
+            marks[c - 300 - 1] = 64                  # the next segment's first cut; its window holds c - 1
+            marks[c - 1] = 100
+            marks[c + 800] = 100                     # the next cut of both
+            lo = c + 800 + 702
+        where[kind] = a
+        a = lo // seg_len + 4
+    n = (a + 2) * seg_len + 555
+    marks.update(_background(lo, n))
+    marks.setdefault(100, 64)                        # the first window's marker
+    return marker_block(n, marks, 740 + seg_len % 97) + (where,)
+
+
+REPAIR_P0 = 1500              # repair_bytes_blocks: the failed chain's last cut, at either segment length
+
+
+@functools.lru_cache(None)
+def repair_bytes_blocks():
+    """(B) segment 0's chain cuts at 702 and 1,500 and then runs three long chunks, the first two
+    ending within the first 701 B of a segment (of either length: no list holds those cuts), the third
+    at REPAIR_P0 + kRepairBytes exactly, a main cut of its segment: the repair merges there.  In the
+    second block that cut is one byte later: the repair gives up and the sequential walk finishes the
+    block from the two cuts the stitch produced.  -> [(block, end offsets)] (exact, one past)."""
+    out = []
+    for extra in (0, 1):
+        c1, c2 = 14040 * 71 + 300, 14040 * 142 + 300
+        c3 = REPAIR_P0 + (2 << 20) + extra
+        assert min(c3 % 2808, c3 % 14040) >= 702 + 2 and max(c1 - REPAIR_P0, c2 - c1) <= MAX_L
+        chunks = [C(702, 5, 10, 5), C(REPAIR_P0 - 702, 7, 3, 7), C(c1 - REPAIR_P0, 100, 8, 110), C(c2 - c1, 100, 8, 110),
+                  C(c3 - c2, 100, 8, 110), C(900, 9, 600, 9), C(5000, 9, 2, 40), C(750, 1, 1, 1)]
+        out.append(designed_block(chunks, 750 + extra, tail=77))
+    return out
+
+
+RQ_KEEP = 16384               # common.hpp kRqKeep
+QUEUE_SURPLUS = 4096
+
+
+@functools.lru_cache(None)
+def queue_batch(blocks=8, surplus=QUEUE_SURPLUS):
+    """(C) one batch at seg_len 2,808 whose failed boundaries number >= kRqKeep + surplus: repairs back
+    to back, every second segment a failed boundary on the block's path, each merging within 2 cuts
+    (n_ext 2, every third 1) except every 97th (n_ext 64, 65, 66, 129 in turn): which of them get queue positions
+    at or above kRqKeep is up to the atomics."""
+    per = -(-(RQ_KEEP + surplus) // blocks)
+    out = []
+    for b in range(blocks):
+        long_r = (64, 65, 66, 129)
+        script = []
+        for i in range(per):
+            script.append(("repair", long_r[(i // 97) % 4] if i % 97 == 96 else (2 if (i + b) % 3 else 1)))
+        out.append(lattice_episodes(2808, 351, script, 760 + b, a0=1 + b % 3, tail_bytes=100 + 17 * b)[:2])
+    return out
+
+
+STITCH_NODES = 1024           # chunk.hip kStitchNodes
+
+
+@functools.lru_cache(None)
+def stitch_windows(seg_len, give_up):
+    """(D) more than 2 x kStitchNodes irregular boundaries in one block: repairs back to back (every
+    jump's target is the next irregular boundary, so the jump from the last node of a window lands on
+    the first node of the next), eight of them passing over two failed boundaries each; the path ends
+    inside the third window: the chain leaves for good and runs to the block end within its overrun
+    (END), or (give_up) fails and its repair runs out of data, so the sequential walk starts from the
+    offsets all three windows produced."""
+    rs = REPAIR_SCRIPTS[(seg_len, 351)]
+    short = [r for r in rs if r < 12]
+    script = []
+    for i in range(2 * STITCH_NODES + 40):
+        script.append(("repair", 64 + i % 3, (1, 2)) if i % 256 == 200 else ("repair", short[i % len(short)]))
+    script.append(("leave",))
+    tail = (6, 77) if give_up else (1, 1500)
+    return lattice_episodes(seg_len, 351, script, 780 + seg_len % 97 + give_up, tail_segs=tail[0], tail_bytes=tail[1])

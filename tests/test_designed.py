@@ -11,7 +11,14 @@ CPU tests: the C oracle and the two Python restatements return exactly the desig
 agrees with the oracle's digests, and the coverage each family claims is asserted as complete sets
 (over chunks that are not their block's last).  GPU tests: every block against Oracle.reduce through
 compare_block / compare_state, bit-exact, and the stored result read back (scrub, verified rebuild,
-ranged reads across designed cuts)."""
+ranged reads across designed cuts).
+
+The bookkeeping families ("Designed bookkeeping") pin where the chunker's speculate /
+repair / stitch steps branch between segments: tests/lane_model.py predicts every segment's cut
+counts, boundary outcome, jump and place in the block's offsets from the rule alone, the CPU tests
+prove from it that each block reaches the branch it was built for (and stops reaching it when one
+constant of the model is changed), and the GPU tests hold the chunker's own per-segment records
+(hdrf_batch_seg_trace) to the model, besides the cuts, digests and stored bytes."""
 import collections
 import hashlib
 import os
@@ -23,6 +30,7 @@ import numpy as np
 import pytest
 
 import designed as D
+import lane_model as LM
 from helpers import compare_block, compare_state
 from hdrf_amd.lib import Context
 from oracle import pyref
@@ -226,6 +234,225 @@ def test_coverage_end_blocks():
     assert {c for c, _ in got} == set(D.END_CLASSES) and {a for _, a in got} == {0, 1, 2, 3} and len(got) == 16
 
 
+# ---- CPU: the bookkeeping model (tests/lane_model.py) and the families built on it ----------------
+K = LM.CONSTANTS
+
+
+def _bookkeeping_blocks(seg):
+    """[(tag, block, designed offsets)] of the bookkeeping families built for seg_len seg (family C apart)."""
+    out = [("overrun_sweep",) + D.overrun_sweep(seg)[:2], ("overrun_edges",) + D.overrun_edges(seg)[:2]]
+    out += [(f"small {i}",) + b for i, b in enumerate(D.small_blocks(seg))]
+    out += [(f"repair d={d} hole={h}",) + D.repair_sweep(L, d, h)[:2] for (L, d) in D.REPAIR_SCRIPTS if L == seg
+            for h in (False, True)]
+    out += [(f"repair_bytes +{i}",) + b for i, b in enumerate(D.repair_bytes_blocks())]
+    out += [(f"stitch give_up={g}",) + D.stitch_windows(seg, g)[:2] for g in (False, True)]
+    return out
+
+
+def test_model_constants_are_the_sources():
+    assert {"kLaneOver", "kRepairBytes", "kRepairCuts", "kRqKeep", "kSegMaxWin", "kStitchNodes"} <= set(K)
+    assert K["kRqKeep"] == D.RQ_KEEP and K["kStitchNodes"] == D.STITCH_NODES
+    assert LM.default_params()["repair_bytes"] == K["kRepairBytes"] == 2 << 20
+    # kRepairCuts cannot bind before kRepairBytes: that many cuts span more than the byte limit
+    assert K["kRepairCuts"] * D.MIN_L > K["kRepairBytes"]
+    # nor can the 64-entry lookup: a segment holds at most kSegMaxWin main cuts
+    assert K["kSegMaxWin"] < 63 and max(D.SEG_LENS) == K["kSegMaxWin"] * D.MIN_L
+
+
+@pytest.mark.parametrize("name", FAMILIES)
+def test_model_offsets_equal_oracle(name):
+    """Following the model's path through its own lists gives the reference's cuts, at both segment lengths."""
+    for tag, blk, offs in _family(name):
+        o = np.asarray(ora_chunk(blk))
+        for seg in D.SEG_LENS:
+            assert np.array_equal(model_of(blk, seg).offsets, o), f"{name} {tag} seg_len {seg}"
+
+
+@pytest.mark.parametrize("seg", D.SEG_LENS)
+def test_bookkeeping_cuts_designed_oracle_model(seg):
+    for tag, blk, offs in _bookkeeping_blocks(seg):
+        o = np.asarray(ora_chunk(blk))
+        assert np.array_equal(o, offs), f"{tag}: the C oracle's cuts are not the designed ones"
+        for s2 in D.SEG_LENS:
+            assert np.array_equal(model_of(blk, s2).offsets, o), f"{tag}: the model's offsets at seg_len {s2}"
+        if len(blk) < 400_000:
+            assert pyref.chunking_closed_form(blk.tobytes()) == o.tolist(), f"{tag}: pyref.chunking_closed_form"
+
+
+def test_coverage_steps_together():
+    """The lanes step together: blocks of the sweeps hold boundaries whose shared cut the next segment
+    had not made yet at that step, so the boundary is not a sync although the lists share the cut."""
+    for seg, names in ((2808, ("chunk_sweep", "fallback_sweeps", "seams")), (14040, ("chunk_sweep", "long_search", "seams"))):
+        for name in names:
+            hits = [h for _, blk, _ in _family(name) for h in [model_of(blk, seg)] if h.passed_unseen()]
+            assert hits, (seg, name)
+            for m in hits:
+                assert all(m.sync[k] < 0 or (m.sync[k] & 0xffff) > i for k, i, _ in m.passed_unseen())
+
+
+def _sync(i, j):
+    return i | (j << 16)
+
+
+@pytest.mark.parametrize("seg", D.SEG_LENS)
+def test_coverage_overrun(seg):
+    """(A) from the model: syncs at overrun cut 1, 2, (3 | 7, 8) with j 0 and non-zero, at segments 62
+    and 63; the cuts at e + seg_len - 1 and e + seg_len; the byte cap; 1- and 2-segment blocks; the
+    last boundary."""
+    blk, _, log = D.overrun_sweep(seg)
+    m = model_of(blk, seg)
+    got = set()
+    for ev, a, _ in log[:-1]:
+        assert m.on_path[a] and m.sync[a] == _sync(ev[1], ev[1]), (ev, a, m.state(a))
+        assert m.over[a][ev[1]] == m.main[a + 1][ev[1]]
+        got.add(ev[1] + 1)
+    # 8 overrun cuts need 7 x 702 B = 4,914 B inside the next segment: more than 2,808
+    assert got == ({1, 2, 3} if seg == 2808 else {1, 2, 3, 7, 8})
+    assert {a for ev, a, _ in log if ev[0] == "sync"} >= {62, 63}
+    assert any(m.sync[k] == _sync(1, 0) for k in range(m.nseg - 1))       # the plain lattice: j = 0 behind i = 1
+    a = log[-1][1]                                                         # the chain that leaves for good
+    assert m.sync[a] == LM.GIVEUP and m.n_over[a] == D.lattice_fail_cuts(seg, 351) and m.fallback and m.term == a
+    assert m.repair_span[a] < K["kRepairBytes"] and len(m.ext[a]) < K["kRepairCuts"]   # the repair ran out of data
+    assert m.rule.next((m.ext[a] or m.over[a])[-1], False) is None
+    assert [model_of(b, seg).nseg for b, _ in D.small_blocks(seg)] == [1, 2, 3]
+    m2 = model_of(D.small_blocks(seg)[1][0], seg)                           # the last boundary of a 2-segment block
+    assert m2.state(0)[1:3] == ((4, LM.END) if seg == 2808 else (8, LM.GIVEUP))
+    blk, _, where = D.overrun_edges(seg)
+    m = model_of(blk, seg)
+    e = {k: (a + 1) * seg for k, a in where.items()}
+    a = where["last_byte"]
+    assert m.sync[a] == _sync(0, 0) and m.over[a] == [e["last_byte"] + seg - 1] and m.on_path[a]
+    a = where["last_byte_capped"]
+    assert m.state(a)[1:6] == (0, LM.JUMP, 1, 0, 1) and m.ext[a] == [e["last_byte_capped"] + seg - 1]
+    a = where["one_past"]
+    c = e["one_past"] + seg
+    assert m.over[a] == [c] and m.state(a)[2:6] == (LM.JUMP, 2, 0, 1) and m.over[a + 1][0] == c
+    a = where["at_over_lim"]
+    assert m.over[a] == [e["at_over_lim"] + seg - 64] and m.sync[a] == LM.JUMP and m.on_path[a]
+    a = where["below_over_lim"]
+    assert m.over[a][0] == e["below_over_lim"] + seg - 65 and m.n_over[a] == 2 and m.sync[a] == LM.JUMP
+
+
+@pytest.mark.parametrize("seg", D.SEG_LENS)
+def test_coverage_repairs(seg):
+    """(B) from the model: the n_ext, jmp and jj values, an off-path repair beside an on-path one, a cut
+    met only as another segment's overrun cut, kRepairBytes exactly and one byte more."""
+    n_ext, jmp, jj_kind = set(), set(), set()
+    for (L, d) in D.REPAIR_SCRIPTS:
+        if L != seg:
+            continue
+        for hole in (False, True):
+            blk, _, log = D.repair_sweep(L, d, hole)
+            m = model_of(blk, seg)
+            assert log[0][1] == (63 if hole else 62)
+            for ev, a, tgt in log:
+                assert m.on_path[a] and m.sync[a] == LM.JUMP and a + m.jmp[a] == tgt, (ev, a, m.state(a))
+                assert m.ext_dst[a] >= 0 and m.n_over[a] == D.lattice_fail_cuts(seg, d)
+                if hole:                                  # met at segment tgt - 1's overrun cut, matched one cut on
+                    c = m.ext[a][-2]
+                    assert c == tgt * seg + 1 == m.over[tgt - 1][0] and c not in m.main[tgt] and m.jj[a] == 0
+                    continue
+                assert m.n_ext[a] == ev[1]
+                n_ext.add(ev[1])
+                jmp.add(min(int(m.jmp[a]), 8))
+                jj_kind |= {("first", "second")[j] for j in (0, 1) if m.jj[a] == j}
+                if m.jj[a] == m.n_main[tgt] - 1:
+                    jj_kind.add("last")
+                if ev[1] >= 64:                           # the boundaries it passes over failed too: nothing to write
+                    for b in (a + 1, a + 2):
+                        assert not m.on_path[b] and m.sync[b] == LM.JUMP and m.n_ext[b] > 1 and m.ext_dst[b] == -1
+    assert n_ext >= set(D.REPAIR_N_EXT) | {1}
+    # jmp 1 needs a repair cut inside the next segment, which the lane walk records itself unless kLaneOver
+    # stops it (14,040 only) or its search was capped (overrun_edges, last_byte_capped)
+    assert jmp >= ({2, 3, 8} if seg == 2808 else {1, 2, 3, 8}) and jj_kind == {"first", "second", "last"}
+    exact, past = (model_of(b, seg) for b, _ in D.repair_bytes_blocks())
+    assert exact.state(0)[2:6] == (LM.JUMP, exact.ext[0][-1] // seg, 0, 3) and exact.repair_span[0] == K["kRepairBytes"]
+    assert not exact.fallback and exact.over[0] == [] and exact.main[0] == [702, D.REPAIR_P0]
+    assert past.sync[0] == LM.GIVEUP and past.repair_span[0] == K["kRepairBytes"] + 1 and past.fail_dst == 2
+
+
+def test_coverage_queue_batch():
+    """(C) from the model: failed boundaries >= kRqKeep + the surplus, short repairs, n_ext on the
+    blocks' paths below and above 64."""
+    blocks = D.queue_batch()
+    ms = [model_of(b, 2808) for b, _ in blocks]
+    assert sum(m.rq_count for m in ms) >= K["kRqKeep"] + D.QUEUE_SURPLUS
+    assert sum(len(b) for b, _ in blocks) < 160_000_000 and max(len(b) for b, _ in blocks) <= 16 << 20
+    for m in ms:
+        on = [int(k) for k in m.failed if m.on_path[k]]
+        ne = collections.Counter(m.n_ext[on].tolist())
+        assert len(on) == m.rq_count and {1, 2, 64, 65, 66, 129} == set(ne) and ne[2] > 1000
+        assert max(m.repair_span.values()) < K["kRepairBytes"] // 16 and not m.fallback
+
+
+@pytest.mark.parametrize("give_up", [False, True])
+@pytest.mark.parametrize("seg", D.SEG_LENS)
+def test_coverage_stitch_windows(seg, give_up):
+    """(D) from the model: more than two windows of irregular boundaries, on and off the path; jumps from
+    the last node of a window to the first of the next; the path ends in the third window."""
+    blk, _, log = D.stitch_windows(seg, give_up)
+    m = model_of(blk, seg)
+    N = K["kStitchNodes"]
+    assert len(m.nodes) > 2 * N and sum(not m.on_path[k] for k in m.nodes) >= 16
+    for w in (1, 2):
+        src, dst = m.nodes[w * N - 1], m.nodes[w * N]
+        assert m.on_path[src] and m.sync[src] == LM.JUMP and src + m.jmp[src] == dst and m.on_path[dst]
+    t = m.term
+    assert 2 * N <= m.node_index(t) < 3 * N and t == log[-1][1] and t < m.nseg - 1
+    if give_up:
+        assert m.sync[t] == LM.GIVEUP and m.fallback and m.fail_dst == int(m.piece.sum()) > 2 * N
+    else:
+        assert m.sync[t] == LM.END and not m.fallback and 0 < m.n_over[t] < D.lattice_fail_cuts(seg, 351)
+
+
+def _changed(blk, seg, **params):
+    """segments whose state a change of one model parameter changes, and the changed model"""
+    a, b = model_of(blk, seg), LM.Model(blk, seg, **params)
+    assert a.nseg == b.nseg
+    return [k for k in range(a.nseg) if a.state(k)[:6] != b.state(k)[:6]], b
+
+
+def test_teeth_each_block_sits_on_its_edge():
+    """One constant of the model changed at a time: the prediction for the block built for that edge
+    changes at the boundary built for it (no kernel is changed or run).  The final offsets never do:
+    every branch leads to the same cuts, which is why only the trace can tell them apart."""
+    # kLaneOver (8 overrun cuts do not fit in 2,808 B: 14,040 only)
+    seg = 14040
+    blk, offs, log = D.overrun_sweep(seg)
+    at8 = [a for ev, a, _ in log if ev == ("sync", 7)]
+    ch, m7 = _changed(blk, seg, lane_over=7)
+    assert set(at8) <= set(ch) and all(m7.sync[a] == LM.JUMP for a in at8) and np.array_equal(m7.offsets, offs)
+    ch, m9 = _changed(blk, seg, lane_over=9)
+    assert not set(ch) & {a for ev, a, _ in log if ev[0] == "sync"}
+    blk, offs, log = D.repair_sweep(seg, 351)
+    a = log[0][1]                                       # n_ext 1: the 9th overrun cut would have been shared
+    ch, m9 = _changed(blk, seg, lane_over=9)
+    assert a in ch and m9.sync[a] == _sync(8, 8) and np.array_equal(m9.offsets, offs)
+    # the lookup width: no list has 63 main cuts (kSegMaxWin = 20), so 63 changes nothing anywhere
+    for s2 in D.SEG_LENS:
+        for tag, b, _ in _bookkeeping_blocks(s2):
+            if not tag.startswith("stitch"):
+                assert _changed(b, s2, lookup=63)[0] == [], tag
+                assert int(model_of(b, s2).n_main.max()) <= K["kSegMaxWin"]
+    # kRepairBytes
+    for seg in D.SEG_LENS:
+        (exact, offs), (past, offs1) = D.repair_bytes_blocks()
+        ch, lo = _changed(exact, seg, repair_bytes=K["kRepairBytes"] - 1)
+        assert 0 in ch and lo.sync[0] == LM.GIVEUP and np.array_equal(lo.offsets, offs)
+        assert 0 not in _changed(exact, seg, repair_bytes=K["kRepairBytes"] + 1)[0]
+        ch, hi = _changed(past, seg, repair_bytes=K["kRepairBytes"] + 1)
+        assert 0 in ch and hi.sync[0] == LM.JUMP and np.array_equal(hi.offsets, offs1)
+        assert 0 not in _changed(past, seg, repair_bytes=K["kRepairBytes"] - 1)[0]
+        # over_lim
+        blk, offs, where = D.overrun_edges(seg)
+        ch, up = _changed(blk, seg, over_lim_delta=16)
+        assert where["at_over_lim"] in ch and up.n_over[where["at_over_lim"]] == 2 and np.array_equal(up.offsets, offs)
+        assert where["last_byte_capped"] in ch and up.sync[where["last_byte_capped"]] == _sync(0, 0)
+        ch, dn = _changed(blk, seg, over_lim_delta=-16)
+        assert where["below_over_lim"] in ch and dn.n_over[where["below_over_lim"]] == 1 and np.array_equal(dn.offsets, offs)
+        assert where["last_byte"] in ch and dn.sync[where["last_byte"]] == LM.JUMP and dn.n_over[where["last_byte"]] == 0
+
+
 # ---- GPU ---------------------------------------------------------------------------------------
 CFG = dict(max_block_bytes=16 << 20, max_batch_blocks=8, index_log2=20, arena_slots=64)
 
@@ -251,12 +478,42 @@ def check_stored(ctx, stored):
             assert np.array_equal(ctx.read_range(bid, lo, 6), blk[lo:lo + 6]), f"block {bid:#x} range at cut {cut}"
 
 
-def reduce_blocks(ctx, ora, blocks, bid0, tag=""):
-    """reduce_block of each (block, designed offsets) against the oracle; -> [(bid, block, offsets)]."""
+_MODELS = {}
+
+
+def model_of(blk, seg_len):
+    """the lane model of a (cached, read-only) designed block"""
+    key = (blk.ctypes.data, len(blk), seg_len)
+    if key not in _MODELS:
+        _MODELS[key] = LM.Model(blk, seg_len)
+    return _MODELS[key]
+
+
+def check_trace(ctx, b, blk, seg_len, tag):
+    """Block b of the batch just completed: the chunker's per-segment records equal the model's, every
+    field of every segment (queue order is not part of them); -> the batch's repair-queue count."""
+    m = model_of(blk, seg_len)
+    tr, rq = ctx.batch_seg_trace(b, m.nseg)
+    assert len(tr["sync"]) == m.nseg, f"{tag}: {len(tr['sync'])} segments, the model has {m.nseg}"
+    want = dict(n_main=m.n_main, n_over=m.n_over, sync=m.sync, jmp=m.jmp, jj=m.jj, n_ext=m.n_ext, ext_dst=m.ext_dst,
+                n_piece=m.piece)
+    for f in ctx.SEG_TRACE_FIELDS:
+        bad = np.flatnonzero(tr[f] != want[f])
+        assert not len(bad), (f"{tag}: {f} differs from the model at segments {bad[:8].tolist()}: "
+                              f"chunker {tr[f][bad[:8]].tolist()}, model {want[f][bad[:8]].tolist()}")
+    assert np.array_equal(tr["n_piece"] > 0, m.on_path & (m.piece > 0)), f"{tag}: segments on the block's path"
+    return rq
+
+
+def reduce_blocks(ctx, ora, blocks, bid0, tag="", seg_len=None):
+    """reduce_block of each (block, designed offsets) against the oracle; -> [(bid, block, offsets)].
+    seg_len: the context's lane-walk segment length; the chunker's trace is then held to the model."""
     stored = []
     for i, (blk, offs) in enumerate(blocks):
         bid = bid0 + 7 * i
         g = ctx.reduce_block(blk, bid)
+        if seg_len is not None:
+            check_trace(ctx, 0, blk, seg_len, f"{tag} block {i}")
         o = ora.reduce(blk, bid)
         compare_block(g, o, tag=f"{tag} block {i}")
         if offs is not None:
@@ -265,7 +522,7 @@ def reduce_blocks(ctx, ora, blocks, bid0, tag=""):
     return stored
 
 
-def reduce_device_batch(ctx, ora, blocks, bids, fill=0, exact=False, tag=""):
+def reduce_device_batch(ctx, ora, blocks, bids, fill=0, exact=False, tag="", seg_len=None):
     """One reduce_batch of blocks placed in device memory at 16-B aligned offsets, the gaps (64..111 B)
     holding `fill`; exact: readable is the contract's minimum, len + 64."""
     offs, o = [], 0
@@ -283,7 +540,9 @@ def reduce_device_batch(ctx, ora, blocks, bids, fill=0, exact=False, tag=""):
         g = ctx.batch_result(i)
         compare_block(g, ora.reduce(blk, bids[i]), tag=f"{tag} batch block {i}")
         assert np.array_equal(g["offsets"], want), f"{tag} batch block {i}: not the designed cuts"
+    rq = [check_trace(ctx, i, blk, seg_len, f"{tag} batch block {i}") for i, (blk, _) in enumerate(blocks)] if seg_len else []
     ctx.dev_free(dev)
+    return rq[0] if rq else None
 
 
 def case_sha_sweep(hasher):
@@ -390,6 +649,7 @@ def test_block_ends_at_contract_minimum():
 
 
 SEGS = [1 << 16, None]        # lane-walk segments of 2,808 B and the default's 14,040 B
+SEG_OF = {1 << 16: 2808, None: 14040}
 
 
 def _chunker_ctx(seg):
@@ -401,14 +661,15 @@ def _chunker_ctx(seg):
 @pytest.mark.parametrize("seg", SEGS)
 @pytest.mark.parametrize("group", ["sweeps", "long", "fallback", "seams", "interleaved"])
 def test_chunker_families(group, seg):
-    """(f) the chunker's general path at designed cuts."""
+    """(f) the chunker's general path at designed cuts; the per-segment trace equals the lane model's
+    (these blocks hold the boundaries where a lane passes a shared cut the next lane has not made yet)."""
     blocks = {"sweeps": lambda: [D.chunk_sweep(), D.threshold_sweep()],
               "long": lambda: [D.long_search(), D.long_threshold()],
               "fallback": lambda: [D.fallback_sweeps()],
               "seams": lambda: [D.seams(U) for U in (65536,) + D.SEG_LENS],
               "interleaved": lambda: [D.interleaved(s, rf) for s in IL_SPACINGS for rf in (None, 1 << 19)]}[group]()
     ctx, ora = _chunker_ctx(seg)
-    stored = reduce_blocks(ctx, ora, blocks, 0x6000, tag=group)
+    stored = reduce_blocks(ctx, ora, blocks, 0x6000, tag=group, seg_len=SEG_OF[seg])
     compare_state(ctx, ora, [s[0] for s in stored])
     check_stored(ctx, stored)
     ctx.close()
@@ -421,6 +682,53 @@ def test_chunker_first_negative_batch(seg):
     ctx, ora = _chunker_ctx(seg)
     bids = [0x7000 + i for i in range(4)]
     reduce_device_batch(ctx, ora, D.first_negative_blocks(), bids, tag="first negative")
+    compare_state(ctx, ora, bids)
+    ctx.close()
+
+
+# ---- GPU: the bookkeeping families, cuts and trace -------------------------------------------------
+BOOK_GROUPS = {
+    # blocks built for both segment lengths run under each: a cut must be right wherever the seams fall
+    "overrun": lambda seg: [b for L in D.SEG_LENS for b in [D.overrun_sweep(L)[:2], D.overrun_edges(L)[:2]] + D.small_blocks(L)],
+    "repair": lambda seg: [D.repair_sweep(L, d, h)[:2] for (L, d) in D.REPAIR_SCRIPTS for h in (False, True)]
+    + D.repair_bytes_blocks(),
+    "stitch": lambda seg: [D.stitch_windows(seg, g)[:2] for g in (False, True)],
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group,hasher,seg", [(g, 1, s) for g in BOOK_GROUPS for s in SEGS] + [("repair", 0, 1 << 16)])
+def test_chunker_bookkeeping(group, hasher, seg):
+    """(A, B, D) every block of the family: the designed cuts, the oracle's block result and state, the
+    stored bytes, and the chunker's per-segment trace (cut counts, sync / jmp / jj / n_ext, ext_dst, the
+    offsets each segment contributed) equal to the lane model's for every segment.  SHA sees nothing
+    new in these chunks, so hasher 0 runs the repair family alone, once."""
+    blocks = BOOK_GROUPS[group](SEG_OF[seg])
+    kw = dict(CFG, max_block_bytes=32 << 20, hasher=hasher)
+    if seg is not None:
+        kw["segment_bytes"] = seg
+    ctx, ora = Context(**kw), Oracle(hasher=hasher)
+    stored = reduce_blocks(ctx, ora, blocks, 0x8000, tag=group, seg_len=SEG_OF[seg])
+    compare_state(ctx, ora, [s[0] for s in stored])
+    check_stored(ctx, stored)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_chunker_queue_beyond_kept_entries():
+    """(C) one batch of 8 blocks at seg_len 2,808 with 20,480 failed boundaries, all on their blocks'
+    paths: the repair queue runs 4,096 entries past kRqKeep, so that many repairs (which ones is up to
+    the queue's atomics) take the emit pass's second walk, n_ext below and above 64 among them, and the
+    rest the kept cuts.  Every cut of every block is judged, and the trace against the model.
+    Host side, measured on the CPU: generation 0.7 s, the oracle (chunking + SHA-224) 0.9 s, the models
+    1.5 s for the 126.6 MB batch."""
+    blocks = D.queue_batch()
+    ctx = Context(hasher=1, **dict(CFG, segment_bytes=1 << 16))
+    ora = Oracle(hasher=1)
+    bids = [0x9000 + i for i in range(len(blocks))]
+    rq = reduce_device_batch(ctx, ora, blocks, bids, tag="queue", seg_len=2808)
+    print(f"repair queue: {rq} entries, kRqKeep {K['kRqKeep']}")
+    assert rq == sum(model_of(b, 2808).rq_count for b, _ in blocks) and rq >= K["kRqKeep"] + 1024
     compare_state(ctx, ora, bids)
     ctx.close()
 
