@@ -14,27 +14,6 @@ static_assert(HDRF_COMPACT_MAX == kCpMax, "HDRF_COMPACT_MAX is compact_plan.hpp'
 
 namespace {
 
-// collect / cover / gather / LZ4 / commit times for scripts/compact_speed.py: HDRF_COMPACT_TIMES=1
-// prints them to stderr (read at every call; changes no result)
-struct CpTimer {
-    bool on = env_int("HDRF_COMPACT_TIMES", 0) != 0;
-    hipEvent_t ev[8] = {};
-    CpTimer()
-    {
-        for (auto &e : ev)
-            if (on && hipEventCreate(&e) != hipSuccess) on = false;
-    }
-    ~CpTimer()
-    {
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int i, hipStream_t st)
-    {
-        if (on) (void)hipEventRecord(ev[i], st);
-    }
-};
-
 // the call's staging: freed on every path
 struct CpStaging {
     uint8_t *p = nullptr;
@@ -100,7 +79,7 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
         }
         r.old_bytes = r.new_bytes = list.valid[i];
     }
-    CpTimer tm;
+    StageTimer tm("HDRF_COMPACT_TIMES", 10);             // collect / cover / gather / LZ4 / commit: scripts/compact_speed.py
     const uint32_t lz_segs = (uint32_t)((cmax + 261099) / 261100);       // launch_lz4's segments per container
     const int wgs = 4 * ctx->n_cu;
     // the first collect run: the containers' counters and the rows of each workgroup
@@ -108,7 +87,7 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
     if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, L.o_lz)) return rc == HDRF_E_HIP ? HDRF_E_NOMEM : rc;
     uint8_t *R = ctx->d_rd;
     CpCount cc[kCpMax] = {};
-    std::vector<uint32_t> wg(kCpMaxWgs, 0);
+    std::vector<uint32_t> wg(kWalkMaxWgs, 0);
     HIPCK(hipMemsetAsync(R, 0, L.o_lz, st));
     tm.mark(0, st);
     HIPCK(launch_cp_collect(ctx->d_tab, log2cap, tag_mask(ctx), list, (CpCount *)(R + L.o_cnt), (uint32_t *)(R + L.o_wg),
@@ -202,7 +181,6 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
     }
     tm.mark(7, st);
     HIPCK(hipStreamSynchronize(st));
-    float t_commit = 0.f;
     int64_t total = 0;
     for (int i = 0; i < n; i++) {
         if (!((go >> i) & 1u)) continue;
@@ -229,9 +207,7 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
     }
 
     // ---- phase B: commit ------------------------------------------------------------------------
-    hipEvent_t eb0 = nullptr, eb1 = nullptr;
-    if (tm.on && (hipEventCreate(&eb0) != hipSuccess || hipEventCreate(&eb1) != hipSuccess)) tm.on = false;
-    if (tm.on) (void)hipEventRecord(eb0, st);
+    tm.mark(8, st);
     hipError_t e = hipSuccess;
     for (int i = 0; i < n && e == hipSuccess; i++) {
         if (!((go >> i) & 1u)) continue;
@@ -242,17 +218,12 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
                                (size_t)rows[i].file_bytes, hipMemcpyDeviceToDevice, st);
     }
     if (e == hipSuccess) e = launch_cp_rewrite(d_rows, (uint32_t)nrows, go, d_map, d_pre, map_words, ctx->d_tab, st);
-    if (tm.on) (void)hipEventRecord(eb1, st);
+    tm.mark(9, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         ctx->lost = true;
-        if (eb0) (void)hipEventDestroy(eb0);
-        if (eb1) (void)hipEventDestroy(eb1);
         return set_err(ctx, HDRF_E_HIP, std::string("hdrf_compact commit: ") + hipGetErrorString(e) + " (hdrf_reset)");
     }
-    if (tm.on) t_commit = elapsed(eb0, eb1);
-    if (eb0) (void)hipEventDestroy(eb0);
-    if (eb1) (void)hipEventDestroy(eb1);
     for (int i = 0; i < n; i++) {
         if (!((go >> i) & 1u)) continue;
         const hdrf_compact_row &r = rows[i];
@@ -278,8 +249,7 @@ extern "C" int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *id
             if ((go >> i) & 1u) moved_bytes += rows[i].new_bytes;
         fprintf(stderr, "hdrf_compact times: collect %.3f ms, cover %.3f ms, gather %.3f ms, lz4 %.3f ms, commit %.3f ms "
                         "(containers %d, rows %llu, gathered bytes %lld)\n",
-                elapsed(tm.ev[0], tm.ev[1]) + elapsed(tm.ev[2], tm.ev[3]), elapsed(tm.ev[3], tm.ev[4]),
-                elapsed(tm.ev[5], tm.ev[6]), lz ? elapsed(tm.ev[6], tm.ev[7]) : 0.f, t_commit, ngo,
+                tm.ms(0, 1) + tm.ms(2, 3), tm.ms(3, 4), tm.ms(5, 6), lz ? tm.ms(6, 7) : 0.f, tm.ms(8, 9), ngo,
                 (unsigned long long)nrows, moved_bytes);
     }
     return ngo;

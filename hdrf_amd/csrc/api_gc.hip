@@ -29,31 +29,6 @@ extern "C" int hdrf_block_delete(hdrf_ctx *ctx, uint64_t block_id)
     return 0;
 }
 
-namespace {
-
-// mark / sweep / rebuild times for scripts/gc_speed.py: HDRF_GC_TIMES=1 prints them to stderr (read at
-// every call; changes no result)
-struct GcTimer {
-    bool on = env_int("HDRF_GC_TIMES", 0) != 0;
-    hipEvent_t ev[6] = {};
-    GcTimer()
-    {
-        for (auto &e : ev)
-            if (on && hipEventCreate(&e) != hipSuccess) on = false;
-    }
-    ~GcTimer()
-    {
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int i, hipStream_t st)
-    {
-        if (on) (void)hipEventRecord(ev[i], st);
-    }
-};
-
-}  // namespace
-
 extern "C" int64_t hdrf_gc(hdrf_ctx *ctx, int32_t flags, hdrf_gc_stats *st_out, hdrf_gc_container *rows, int64_t cap)
 {
     HDRF_LOCK(ctx);
@@ -81,7 +56,7 @@ extern "C" int64_t hdrf_gc(hdrf_ctx *ctx, int32_t flags, hdrf_gc_stats *st_out, 
     for (auto &kv : ctx->containers) idset.insert(kv.first);
     for (auto &kv : ctx->loaded) idset.insert(kv.first);
     hipStream_t st = ctx->st;
-    GcTimer tm;
+    StageTimer tm("HDRF_GC_TIMES", 5);                   // mark / sweep / rebuild: scripts/gc_speed.py
     GcCounters c{};
     GcLayout L{};
     std::vector<uint32_t> cids;
@@ -182,7 +157,7 @@ extern "C" int64_t hdrf_gc(hdrf_ctx *ctx, int32_t flags, hdrf_gc_stats *st_out, 
     }
     if (tm.on) {
         fprintf(stderr, "hdrf_gc times: mark %.3f ms, sweep %.3f ms, rebuild %.3f ms (entries %lld, kept %lld, digests %lld)\n",
-                elapsed(tm.ev[0], tm.ev[1]), elapsed(tm.ev[1], tm.ev[2]), dry ? 0.f : elapsed(tm.ev[3], tm.ev[4]),
+                tm.ms(0, 1), tm.ms(1, 2), dry ? 0.f : tm.ms(3, 4),
                 (long long)S.entries, (long long)S.kept, (long long)S.recipe_digests);
     }
     const int64_t nout = std::min<int64_t>(cap, (int64_t)out.size());

@@ -801,10 +801,7 @@ extern "C" int64_t hdrf_gx_read_fill(hdrf_ctx *ctx, const uint32_t *loc, int64_t
     if (n < 0 || (n && !loc)) return set_err(ctx, HDRF_E_INVAL, "bad fill arguments");
     if (ctx->gx_nfront != ctx->gx_nback) return set_err(ctx, HDRF_E_INVAL, "hdrf_gx_read_fill: a batch is in flight");
     if (int rc = gx_sync_locked(ctx)) return rc;
-    struct RdChunkH { uint32_t slot, start, len, off; };
-    static_assert(sizeof(RdChunkH) == 16, "RdChunk layout");
-    if (rd_chunk_bytes() != sizeof(RdChunkH)) return set_err(ctx, HDRF_E_DEVICE, "RdChunk layout");
-    std::vector<RdChunkH> mine;
+    std::vector<RdChunk> mine;
     std::vector<uint64_t> bases;
     std::map<uint32_t, uint32_t> base_of;               // container id -> index in bases
     uint64_t off = 0, filled = 0;
@@ -821,20 +818,20 @@ extern "C" int64_t hdrf_gx_read_fill(hdrf_ctx *ctx, const uint32_t *loc, int64_t
                 bases.push_back((uint64_t)(uintptr_t)(ctx->d_arena + (size_t)it->second.slot * ctx->cfg.container_max));
             }
             if ((uint64_t)r[2] > ctx->cfg.container_max) return set_err(ctx, HDRF_E_DEVICE, "chunk beyond its container");
-            mine.push_back(RdChunkH{b->second, r[1], len, (uint32_t)off});
+            mine.push_back(RdChunk{b->second, r[1], len, (uint32_t)off});
             filled += len;
         }
         off += len;
     }
     if ((int64_t)off > cap || (off && !dev_out)) return set_err(ctx, HDRF_E_CAPACITY, "output capacity");
     if (!mine.empty()) {
-        const uint64_t o_b = ((mine.size() * sizeof(RdChunkH)) + 255) & ~255ull;
+        const uint64_t o_b = ((mine.size() * sizeof(RdChunk)) + 255) & ~255ull;
         if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, o_b + bases.size() * 8 + 256)) return rc;
         uint8_t *R = ctx->d_rd;
         hipStream_t st = ctx->st;
-        HIPCK(hipMemcpyAsync(R, mine.data(), mine.size() * sizeof(RdChunkH), hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(R, mine.data(), mine.size() * sizeof(RdChunk), hipMemcpyHostToDevice, st));
         HIPCK(hipMemcpyAsync(R + o_b, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, st));
-        HIPCK(launch_rd_gather(R, (int)mine.size(), (const uint64_t *)(R + o_b), dev_out, st));
+        HIPCK(launch_rd_gather((const RdChunk *)R, (int)mine.size(), (const uint64_t *)(R + o_b), dev_out, st));
         HIPCK(hipStreamSynchronize(st));
     }
     return (int64_t)filled;

@@ -10,26 +10,13 @@
 #include "read_plan.hpp"
 
 // ---- index views ------------------------------------------------------------------------
-static void encode_value(const IndexEntry &e, uint8_t v[11])
-{
-    // chunkMeta.getMeta — DN/chunkMeta.java:62-77
-    v[0] = (uint8_t)e.ncopy;
-    v[1] = (uint8_t)(e.cid >> 16); v[2] = (uint8_t)(e.cid >> 8); v[3] = (uint8_t)e.cid;
-    v[4] = (uint8_t)(e.start >> 16); v[5] = (uint8_t)(e.start >> 8); v[6] = (uint8_t)e.start;
-    v[7] = (uint8_t)(e.stop >> 16); v[8] = (uint8_t)(e.stop >> 8); v[9] = (uint8_t)e.stop;
-    v[10] = (uint8_t)(((e.start >> 20) & 0xF0) | ((e.stop >> 24) & 0x0F));
-}
-
+// an entry's digest bytes (index_entry.hpp: the words are little-endian loads of them)
 static void entry_digest(const IndexEntry &e, int H, uint8_t *out)
 {
-    if (H == 20) {                                   // SHA-1: bytes 0..7 kept in dig[3..4]
-        std::memcpy(out, &e.dig[3], 8);
-    } else {                                         // SHA-224: bytes 0..6 in the tag, 7 in ncopy
-        const unsigned long long t = e.tag & kTag56;
-        std::memcpy(out, &t, 7);
-        out[7] = (uint8_t)(e.ncopy >> 8);
-    }
-    std::memcpy(out + 8, e.dig, H == 20 ? 12 : H - 8);
+    uint32_t dw[7];
+    if (H == 20) entry_digest_words<5>(e.tag, e.ncopy, e.dig, dw);
+    else entry_digest_words<7>(e.tag, e.ncopy, e.dig, dw);
+    std::memcpy(out, dw, (size_t)H);
 }
 
 extern "C" int hdrf_index_get(hdrf_ctx *ctx, const uint8_t *digest, uint8_t out11[11])
@@ -49,7 +36,7 @@ extern "C" int hdrf_index_get(hdrf_ctx *ctx, const uint8_t *digest, uint8_t out1
         uint8_t full[28];
         entry_digest(e, ctx->H, full);
         if (e.tag == tag && std::memcmp(full, digest, ctx->H) == 0) {
-            if (out11) encode_value(e, out11);
+            if (out11) encode_value(e.ncopy, e.cid, e.start, e.stop, out11);
             return 1;
         }
         h = (h + 1) & mask;
@@ -117,7 +104,7 @@ extern "C" int64_t hdrf_index_dump(hdrf_ctx *ctx, uint8_t *keys, uint8_t *vals, 
         if (!tag_live(e.tag, key)) continue;
         std::vector<uint8_t> r(H + 11);
         entry_digest(e, H, r.data());
-        encode_value(e, r.data() + H);
+        encode_value(e.ncopy, e.cid, e.start, e.stop, r.data() + H);
         rows.push_back(std::move(r));
     }
     if ((int64_t)rows.size() > cap) return set_err(ctx, HDRF_E_CAPACITY, "index dump capacity");
@@ -476,7 +463,7 @@ static int64_t reconstruct_body(hdrf_ctx *ctx, const uint8_t *recipe, int64_t re
     const std::vector<uint64_t> &base = rd.base;
     const int ncont = (int)cid.size();
     const uint64_t o_dig = 0, dig_b = (uint64_t)n * ctx->HW * 4;
-    const uint64_t o_ch = (dig_b + 255) & ~255ull, ch_b = (uint64_t)n * rd_chunk_bytes();
+    const uint64_t o_ch = (dig_b + 255) & ~255ull, ch_b = (uint64_t)n * sizeof(RdChunk);
     const uint64_t o_base = (o_ch + ch_b + 255) & ~255ull, base_b = (uint64_t)std::max(1, ncont) * 8;
     const uint64_t o_cid = (o_base + base_b + 255) & ~255ull, cid_b = (uint64_t)std::max(1, ncont) * 4;
     const uint64_t o_tot = (o_cid + cid_b + 255) & ~255ull;
@@ -493,19 +480,19 @@ static int64_t reconstruct_body(hdrf_ctx *ctx, const uint8_t *recipe, int64_t re
     HIPCK(hipMemsetAsync(R + o_tot, 0, 16, st));
     const uint64_t *bases = (const uint64_t *)(R + o_base);
     HIPCK(launch_reconstruct(ctx->cfg.hasher, (const uint32_t *)(R + o_dig), (int)n, ctx->d_tab, ctx->cfg.index_log2,
-                             tag_mask(ctx), (const uint32_t *)(R + o_cid), bases, ncont, R + o_ch,
+                             tag_mask(ctx), (const uint32_t *)(R + o_cid), bases, ncont, (RdChunk *)(R + o_ch),
                              (uint64_t *)(R + o_tot), dev_out, (int *)(R + o_tot + 8), st, false));
     uint64_t tot[2] = {0, 0};
     HIPCK(hipMemcpyAsync(tot, R + o_tot, 16, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
     if ((int)tot[1]) return set_err(ctx, HDRF_E_NOTFOUND, "a recipe digest or its container is not readable");
     if ((int64_t)tot[0] != size) return set_err(ctx, HDRF_E_DEVICE, "chunk lengths do not add up to the recipe size");
-    HIPCK(launch_reconstruct(ctx->cfg.hasher, nullptr, (int)n, nullptr, 0, 0, nullptr, bases, 0, R + o_ch, nullptr,
+    HIPCK(launch_reconstruct(ctx->cfg.hasher, nullptr, (int)n, nullptr, 0, 0, nullptr, bases, 0, (RdChunk *)(R + o_ch), nullptr,
                              dev_out, nullptr, st, true));
     VfCounters vc{};
     if (verify) {
         HIPCK(hipMemsetAsync(R + o_vf, 0, sizeof vc, st));
-        HIPCK(launch_vf_hash_block(ctx->cfg.hasher, R + o_ch, (int)n, (const uint32_t *)(R + o_dig), dev_out,
+        HIPCK(launch_vf_hash_block(ctx->cfg.hasher, (const RdChunk *)(R + o_ch), (int)n, (const uint32_t *)(R + o_dig), dev_out,
                                    (uint64_t)size, (VfCounters *)(R + o_vf), vf_workgroups(ctx), st));
         HIPCK(hipMemcpyAsync(&vc, R + o_vf, sizeof vc, hipMemcpyDeviceToHost, st));
     }
@@ -514,12 +501,12 @@ static int64_t reconstruct_body(hdrf_ctx *ctx, const uint8_t *recipe, int64_t re
     if (verify && vc.n_bad) {
         const uint32_t k = ~vc.first_bad_inv;
         *bad_chunk = k;
-        uint32_t c[4] = {0, 0, 0, 0};                  // RdChunk {readable index, start, len, block offset}
-        HIPCK(hipMemcpy(c, R + o_ch + (uint64_t)k * rd_chunk_bytes(), sizeof c, hipMemcpyDeviceToHost));
-        const std::string where = c[0] < cid.size() ? "container " + std::to_string(cid[c[0]]) : std::string("no container");
+        RdChunk c{};
+        HIPCK(hipMemcpy(&c, R + o_ch + (uint64_t)k * sizeof c, sizeof c, hipMemcpyDeviceToHost));
+        const std::string where = c.slot < cid.size() ? "container " + std::to_string(cid[c.slot]) : std::string("no container");
         return set_err(ctx, HDRF_E_CORRUPT,
                        "recipe position " + std::to_string(k) + ": digest " + hex_digest(recipe + 4 + (size_t)k * ctx->H, ctx->H) +
-                           ", " + where + " [" + std::to_string(c[1]) + ", " + std::to_string(c[1] + c[2]) +
+                           ", " + where + " [" + std::to_string(c.start) + ", " + std::to_string(c.start + c.len) +
                            "): the bytes hash to another digest (" + std::to_string(vc.n_bad) + " of " +
                            std::to_string(n) + " chunks of the block)");
     }
@@ -643,7 +630,7 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
     Readable rd;
     readable_list(ctx, rd);
     const uint32_t ncont = (uint32_t)rd.cid.size();
-    const ReadLayout L = read_layout((uint32_t)n, ncont, dig_bytes, px.rows, (uint32_t)rv_chunk_bytes());
+    const ReadLayout L = read_layout((uint32_t)n, ncont, dig_bytes, px.rows, (uint32_t)sizeof(RdChunk));
     if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, L.total)) return rc == HDRF_E_HIP ? HDRF_E_NOMEM : rc;
     uint8_t *R = ctx->d_rd;
     std::vector<uint8_t> up(L.upload, 0);
@@ -663,7 +650,7 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
     HIPCK(hipMemsetAsync(R + L.o_status, 0, (size_t)n * 4, st));
     HIPCK(launch_readv(ctx->cfg.hasher, (const ReadDesc *)(R + L.o_desc), n, (uint32_t)px.rows, (uint32_t)px.tiles, T,
                        ctx->d_tab, ctx->cfg.index_log2, tag_mask(ctx), (const uint32_t *)(R + L.o_cid),
-                       (const uint64_t *)(R + L.o_base), (int)ncont, R + L.o_rows, (int *)(R + L.o_status), st));
+                       (const uint64_t *)(R + L.o_base), (int)ncont, (RdChunk *)(R + L.o_rows), (int *)(R + L.o_status), st));
     HIPCK(hipMemcpyAsync(status.data(), R + L.o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
     int first = 0;

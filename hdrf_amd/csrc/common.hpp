@@ -6,11 +6,13 @@
 //   offsets              [block][cap_blk] u32 chunk END offsets (reference chunking() output)
 //   digests              [block][cap_blk][H] bytes
 //   chunk meta           [block][cap_blk] slot / flags / prefix
-//   index table          2^k entries x 64 B, open addressing keyed by the first 8 digest bytes
+//   index table          2^k entries x 64 B, open addressing keyed by the first 8 digest bytes (index_entry.hpp)
 //   container arena      slots x container_max bytes (raw containers, DataDeduplicator.maxSize)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "index_entry.hpp"
 
 namespace hdrf {
 
@@ -28,61 +30,7 @@ constexpr int kRqKeep = 16384;       // repair-queue entries whose cuts the coun
 constexpr int kSegMinWin = 4;        // seg_len bounds, in units of window + 2 (702 B)
 constexpr int kSegMaxWin = 20;        // seg_len / 702 + 2 + kLaneOver <= kLdsCuts
 
-// Index entry: 64 B.  tag = the table generation ("epoch", 1..255) in bits 56..63 over the first 7
-// digest bytes; an entry whose tag carries another epoch is EMPTY, so a fresh index (hdrf_reset)
-// is one epoch bump instead of 2^k x 64 B of zero stores (a real clear only every 255 resets and
-// at open).  `dig` holds digest bytes 8..27; the 8th digest byte lives in dig[4] (SHA-1: dig[3..4]
-// hold bytes 0..7) or in ncopy bits 8..15 (SHA-224).  ncopy (bits 0..7) / cid / start / stop are
-// the 11-byte Redis value (chunkMeta.getMeta, DN/chunkMeta.java:62-77) in unpacked form.
-struct alignas(64) IndexEntry {
-    unsigned long long tag;
-    unsigned long long mask;    // batch-local: bit b = block b of the batch holds the digest
-    unsigned long long first;   // batch-local: max over ((63-b)<<32 | chunk index)
-    uint32_t batch;             // batch id that created the entry (ids only grow over a context's life)
-    uint32_t ncopy;             // bits 0..7 nCopy, bits 8..15 digest byte 7 (SHA-224)
-    uint32_t cid;
-    uint32_t start;
-    uint32_t stop;
-    uint32_t dig[5];
-
-};
-static_assert(sizeof(IndexEntry) == 64, "IndexEntry must be one 64-B line");
-
-// Tag key of a table: (epoch << 56) | the tag-bit mask (all ones except under the collision test
-// hook, debug_tag_bits).  tag_word: the entry tag a digest must carry; tag_live: an entry of the
-// current epoch; tag_home: the digest's home slot (independent of the epoch).
-constexpr unsigned long long kTag56 = 0x00FFFFFFFFFFFFFFull;
-__host__ __device__ __forceinline__ unsigned long long tag_word(const uint32_t *dw, unsigned long long key)
-{
-    return ((((unsigned long long)dw[0] | ((unsigned long long)dw[1] << 32)) & key) & kTag56) | (key & ~kTag56);
-}
-__host__ __device__ __forceinline__ bool tag_live(unsigned long long t, unsigned long long key)
-{
-    return ((t ^ key) >> 56) == 0;
-}
-__host__ __device__ __forceinline__ uint64_t tag_home(unsigned long long t, int log2cap)
-{
-    return ((t & kTag56) * 0x9E3779B97F4A7C15ull) >> (64 - log2cap);
-}
-// the full digest equals the entry's (the caller matched the tag word: bytes 0..6)
-template <int HW>
-__host__ __device__ __forceinline__ bool entry_matches(const IndexEntry &e, const uint32_t *dw)
-{
-#pragma unroll
-    for (int i = 2; i < HW; i++)
-        if (e.dig[i - 2] != dw[i]) return false;
-    if (HW == 5) return e.dig[3] == dw[0] && e.dig[4] == dw[1];
-    return ((e.ncopy >> 8) & 0xffu) == (dw[1] >> 24);
-}
-// a claimed entry's digest bytes (nCopy is written by the chunk that SETs the value)
-template <int HW>
-__device__ __forceinline__ void store_dig(IndexEntry *e, const uint32_t *dw)
-{
-#pragma unroll
-    for (int i = 2; i < HW; i++) e->dig[i - 2] = dw[i];
-    if (HW == 5) { e->dig[3] = dw[0]; e->dig[4] = dw[1]; }
-    else e->ncopy = (dw[1] >> 24) << 8;
-}
+// (IndexEntry, its tag words and its digest / value codec: index_entry.hpp, shared with the host)
 // nCopy (bits 0..7 of ncopy) without touching the SHA-224 digest byte above it
 __device__ __forceinline__ void set_ncopy(IndexEntry *e, uint32_t n)
 {
@@ -244,6 +192,73 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
         if (l >= d) v += t;
     }
     return v;
+}
+
+// Wave-wide u64 sum (all lanes participate; every lane holds the result).
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// One step of a 1024-thread workgroup's running exclusive scan: use(off) gets the sum of the earlier
+// steps' values and of this step's v over the threads below this one, then *s_carry advances by the
+// step's total.  Every thread calls it, in uniform control flow; s_w: LDS [16], *s_carry: LDS, set
+// behind a barrier before the first step and holding the grand total behind the last one.  use()
+// stores what the offset yields, and it runs BEFORE the two barriers that move the carry: a store
+// issued behind them is still in flight when the next step waits for its load, and the single
+// workgroup of rd_scan, 138 dependent steps for a 128 MiB block, then ran 17 us longer per block.
+template <class F>
+__device__ __forceinline__ void wg1024_excl_scan(uint32_t v, uint32_t *s_w, unsigned long long *s_carry, F use)
+{
+    const int t = (int)threadIdx.x;
+    const uint32_t incl = wave_incl_scan(v);
+    if (lane_id() == 63) s_w[t >> 6] = incl;
+    __syncthreads();
+    uint32_t add = 0, tot = 0;
+    for (int i = 0; i < 16; i++) {
+        if (i < (t >> 6)) add += s_w[i];
+        tot += s_w[i];
+    }
+    const unsigned long long carry = *s_carry;
+    use(carry + add + incl - v);
+    __syncthreads();
+    if (t == 0) *s_carry = carry + tot;
+    __syncthreads();
+}
+
+// Searches of an ascending list given by key(i) (a lambda: the list may sit in LDS, in memory, or in
+// both, as gc_sweep's id list does).  find_sorted: the index in [lo, hi) whose key is v, or -1.
+template <class K>
+__device__ __forceinline__ int find_sorted(int lo, int hi, uint32_t v, K key)
+{
+    const int end = hi;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key(mid) < v) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && key(lo) == v ? lo : -1;
+}
+// the place of container `cid` in the readable container list (sorted by id), or -1
+__device__ __forceinline__ int find_cid(const uint32_t *cids, int ncont, uint32_t cid)
+{
+    return find_sorted(0, ncont, cid, [&](int m) { return cids[m]; });
+}
+// the last r in [0, n) with key(r) <= v (key(0) <= v)
+template <class K>
+__device__ __forceinline__ uint32_t last_le(uint32_t n, uint32_t v, K key)
+{
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        if (key(mid) <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 __device__ __forceinline__ unsigned long long ballot64(bool p) { return __ballot(p); }

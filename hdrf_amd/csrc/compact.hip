@@ -3,8 +3,8 @@
 // The call names up to kCpMax closed containers (CpList, by value: the ids are searched in scalar
 // registers).  What remains of each is the chunks that live index entries name, packed to the front
 // in their old order.  No pass sorts: the order is kept by a cover map of one bit per container byte.
-//   cp_collect — a streaming pass over the table, one lane per 64-B entry, tile-transposed through
-//                LDS as gc_sweep does.  A live entry of a listed container adds to the container's
+//   cp_collect — a streaming pass over the table, one lane per 64-B entry: table_walk.hpp's walk,
+//                shared with gc_sweep.  A live entry of a listed container adds to the container's
 //                counters (held in LDS, flushed once per workgroup) and becomes rows (compact_plan.hpp):
 //                one per kCpPiece bytes.  It runs twice with the same grid: the first run only counts
 //                the rows of each workgroup, so the second appends from a row base of its own
@@ -13,13 +13,13 @@
 //                the container and makes no row, so every later pass stays inside the container.
 //   cp_cover   — one wave per row sets the row's bits: whole words are plain 16-B-wide vector stores
 //                of ones, the two edge words atomicOr (neighbouring chunks share a word).
-//   cp_scan    — eight workgroups per container: popcount and exclusive prefix over the map's words.
+//   cp_scan    — eight workgroups per container: popcount and exclusive prefix over the map's words
+//                (the scan step is common.hpp's wg1024_excl_scan, shared with rd_scan and rv_scan).
 //                The popcount of a map differs from the sum of its ranges exactly when two overlap.
 //   cp_moved   — one lane per row: the entries whose start changes, per container.
 //   cp_gather  — one wave per row: old[a, b) -> image[new(a), ...), new(a) = prefix[a / 32] +
-//                popc(word & low mask).  16-B nontemporal loads and stores with a head and a tail, any
-//                alignment on both sides (the copy discipline of rd_gather / wave_copy; the bytes are
-//                touched once).
+//                popc(word & low mask).  wave_copy<true> (bytes.hpp): 16-B nontemporal loads and stores
+//                with a head and a tail, any alignment on both sides; the bytes are touched once.
 //   cp_rewrite — one lane per row that carries a table slot: the entry's new start / stop, those
 //                two words only.
 #include <algorithm>
@@ -27,19 +27,9 @@
 #include "bytes.hpp"
 #include "compact_plan.hpp"
 #include "launchers.hpp"
+#include "table_walk.hpp"
 
 namespace hdrf {
-
-__device__ __forceinline__ unsigned long long cp_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 
 // new position of old byte p of a container whose map and prefix arrays are given (bit p is set)
 __device__ __forceinline__ uint32_t cp_newpos(const uint32_t *__restrict__ map, const uint32_t *__restrict__ pre, uint32_t p)
@@ -57,37 +47,19 @@ __global__ void __launch_bounds__(256) cp_collect_kernel(const IndexEntry *__res
                                                          CpRow *__restrict__ rows, uint64_t row_cap,
                                                          uint32_t *__restrict__ err)
 {
-    __shared__ uint4 s_e[4][256];                              // per wave: its 64 entries, 4 KiB
     __shared__ uint32_t s_row;                                 // the workgroup's next row
     __shared__ unsigned long long s_bytes[kCpMax];
     __shared__ uint32_t s_chunks[kCpMax], s_bad[kCpMax];
-    const int t = (int)threadIdx.x, w = wave_id(), l = lane_id();
+    const int t = (int)threadIdx.x, l = lane_id();
     if (t < kCpMax) { s_bytes[t] = 0; s_chunks[t] = 0; s_bad[t] = 0; }
     if (t == 0) s_row = 0;
     __syncthreads();
-    if (kEmit) {                                               // the rows of the workgroups before this one
-        unsigned long long before = 0;
-        for (uint32_t y = (uint32_t)t; y < blockIdx.x; y += 256u) before += wg[y];
-        before = cp_wave_sum(before);
-        if (l == 0 && before) atomicAdd(&s_row, (uint32_t)before);
+    if (kEmit) {
+        const uint32_t before = wg_row_base(wg);
+        if (l == 0 && before) atomicAdd(&s_row, before);
         __syncthreads();
     }
-    const uint64_t tstride = (uint64_t)gridDim.x * 256u;
-    // lane l's four 16-B pieces of the wave's 64 entries of a tile: piece k is bytes [(k * 64 + l) * 16, +16)
-    auto fetch = [&](uint64_t tile, uint4 r[4]) {
-        const uint8_t *wb = (const uint8_t *)(tab + tile + (uint64_t)w * 64);
-#pragma unroll
-        for (int k = 0; k < 4; k++) r[k] = ld16_nt(wb + (size_t)(k * 64 + l) * 16);
-    };
-    uint4 r[4] = {};
-    if ((uint64_t)blockIdx.x * 256u < nslots) fetch((uint64_t)blockIdx.x * 256u, r);
-    for (uint64_t tile = (uint64_t)blockIdx.x * 256u; tile < nslots; tile += tstride) {   // uniform
-#pragma unroll
-        for (int k = 0; k < 4; k++) s_e[w][k * 64 + l] = r[k];
-        __syncthreads();
-        const uint4 p0 = s_e[w][l * 4], p2 = s_e[w][l * 4 + 2];
-        __syncthreads();                                       // (the next tile's stores come after every read)
-        if (tile + tstride < nslots) fetch(tile + tstride, r); // in flight while this tile is classified
+    table_walk(tab, nslots, [&](uint64_t slot, uint4 p0, uint4, uint4 p2, uint4) {
         const unsigned long long tag = (unsigned long long)p0.x | ((unsigned long long)p0.y << 32);
         const uint32_t cid = p2.x, start = p2.y, stop = p2.z;
         int j = -1;
@@ -109,7 +81,7 @@ __global__ void __launch_bounds__(256) cp_collect_kernel(const IndexEntry *__res
         // one LDS atomic per wave: the wave's rows, lane by lane
         const uint32_t incl = wave_incl_scan(np);
         const uint32_t wtot = rdlane(incl, 63);
-        if (wtot == 0) continue;                               // (uniform per wave; no barrier below)
+        if (wtot == 0) return;                                 // (uniform per wave)
         uint32_t base = 0;
         if (l == 0) base = atomicAdd(&s_row, wtot);
         base = rdfirst(base) + incl - np;
@@ -119,10 +91,10 @@ __global__ void __launch_bounds__(256) cp_collect_kernel(const IndexEntry *__res
                 if (row >= row_cap) { atomicOr(err, 1u); break; }   // (never: the first run counted them)
                 const uint32_t a = start + k * kCpPiece;
                 const uint32_t b = stop - a > kCpPiece ? a + kCpPiece : stop;
-                st16(rows + row, make_uint4(k ? kCpNoSlot : (uint32_t)(tile + (uint64_t)t), (uint32_t)j, a, b));
+                st16(rows + row, make_uint4(k ? kCpNoSlot : (uint32_t)slot, (uint32_t)j, a, b));
             }
         }
-    }
+    });
     __syncthreads();
     if (!kEmit) {
         if (t == 0) wg[blockIdx.x] = s_row;
@@ -182,7 +154,7 @@ __global__ void __launch_bounds__(1024) cp_scan_kernel(const uint32_t *__restric
         const uint4 m = ld16(map + k);
         before += __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
     }
-    before = cp_wave_sum(before);
+    before = wave_sum_u64(before);
     if (lane_id() == 0 && before) atomicAdd(&s_carry, before);
     __syncthreads();
     const unsigned long long first = s_carry;
@@ -198,25 +170,15 @@ __global__ void __launch_bounds__(1024) cp_scan_kernel(const uint32_t *__restric
         }
         const uint32_t c0 = __popc(m.x), c1 = __popc(m.y), c2 = __popc(m.z), c3 = __popc(m.w);
         const uint32_t v = c0 + c1 + c2 + c3;
-        const uint32_t incl = wave_incl_scan(v);
-        if (lane_id() == 63) s_w[t >> 6] = incl;
-        __syncthreads();
-        uint32_t add = 0, tot = 0;
-        for (int i = 0; i < 16; i++) {
-            if (i < (t >> 6)) add += s_w[i];
-            tot += s_w[i];
-        }
-        const unsigned long long carry = s_carry;
-        const uint32_t e0 = (uint32_t)carry + add + incl - v;
-        if (k + 4 <= nw) st16(pre + k, make_uint4(e0, e0 + c0, e0 + c0 + c1, e0 + c0 + c1 + c2));
-        else if (k < nw) {
-            pre[k] = e0;
-            if (k + 1 < nw) pre[k + 1] = e0 + c0;
-            if (k + 2 < nw) pre[k + 2] = e0 + c0 + c1;
-        }
-        __syncthreads();
-        if (t == 0) s_carry = carry + tot;
-        __syncthreads();
+        wg1024_excl_scan(v, s_w, &s_carry, [&](unsigned long long off) {
+            const uint32_t e0 = (uint32_t)off;
+            if (k + 4 <= nw) st16(pre + k, make_uint4(e0, e0 + c0, e0 + c0 + c1, e0 + c0 + c1 + c2));
+            else if (k < nw) {
+                pre[k] = e0;
+                if (k + 1 < nw) pre[k + 1] = e0 + c0;
+                if (k + 2 < nw) pre[k + 2] = e0 + c0 + c1;
+            }
+        });
     }
     if (t == 0 && s_carry != first) atomicAdd(&cc[c].covered, s_carry - first);    // (cleared by the caller)
 }
@@ -242,35 +204,6 @@ __global__ void __launch_bounds__(256) cp_moved_kernel(const CpRow *__restrict__
     if (t < kCpMax && s_m[t]) atomicAdd(&cc[t].moved, (unsigned long long)s_m[t]);
 }
 
-// wave-cooperative streaming copy of n bytes (any alignment on both sides; 16-B aligned destination
-// words): wave_copy (bytes.hpp) with nontemporal loads and stores
-__device__ inline void cp_wave_copy(uint8_t *dst, const uint8_t *src, uint32_t n)
-{
-    const uint32_t l = (uint32_t)lane_id();
-    uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
-    if (head > n) head = n;
-    if (l < head) wr8(dst + l, rd8(src + l));
-    uint8_t *d = dst + head;
-    const uint8_t *sp = src + head;
-    const uint32_t n16 = (n - head) >> 4;
-    const int sh = (int)((uintptr_t)sp & 15);
-    const uint8_t *sa = sp - sh;
-    uint32_t i = l;
-    for (; i + 192 < n16; i += 256) {                          // four 16-B words per lane in flight
-        const uint4 v0 = load16_shift<true>(sa + 16 * (size_t)i, sh);
-        const uint4 v1 = load16_shift<true>(sa + 16 * (size_t)(i + 64), sh);
-        const uint4 v2 = load16_shift<true>(sa + 16 * (size_t)(i + 128), sh);
-        const uint4 v3 = load16_shift<true>(sa + 16 * (size_t)(i + 192), sh);
-        st16_t<true>(d + 16 * (size_t)i, v0);
-        st16_t<true>(d + 16 * (size_t)(i + 64), v1);
-        st16_t<true>(d + 16 * (size_t)(i + 128), v2);
-        st16_t<true>(d + 16 * (size_t)(i + 192), v3);
-    }
-    for (; i < n16; i += 64) st16_t<true>(d + 16 * (size_t)i, load16_shift<true>(sa + 16 * (size_t)i, sh));
-    const uint32_t tb = head + 16 * n16;
-    for (uint32_t k = tb + l; k < n; k += 64) wr8(dst + k, rd8(src + k));
-}
-
 // grid ceil(nrows / 4) x 256: wave w of the workgroup copies row 4 * blockIdx.x + w, if the row's
 // container is one of `go` (bit j: container j is compacted; the others' maps may be inconsistent)
 __global__ void __launch_bounds__(256) cp_gather_kernel(const CpRow *__restrict__ rows, uint32_t nrows, uint32_t go,
@@ -285,7 +218,7 @@ __global__ void __launch_bounds__(256) cp_gather_kernel(const CpRow *__restrict_
     const uint32_t j = rdfirst(rw.y), a = rdfirst(rw.z), b = rdfirst(rw.w);
     if (!((go >> j) & 1u)) return;
     const uint32_t na = cp_newpos(maps + (uint64_t)j * map_words, pres + (uint64_t)j * map_words, a);
-    cp_wave_copy(img + (uint64_t)j * img_stride + na, (const uint8_t *)(uintptr_t)bases[j] + a, b - a);
+    wave_copy<true>(img + (uint64_t)j * img_stride + na, (const uint8_t *)(uintptr_t)bases[j] + a, b - a);
 }
 
 // one lane per row with a slot, of the containers `go`: tab[slot].start / .stop <- the new range
@@ -305,18 +238,11 @@ __global__ void __launch_bounds__(256) cp_rewrite_kernel(const CpRow *__restrict
     e->stop = ns + len;
 }
 
-static dim3 cp_collect_grid(int log2cap, int wgs)
-{
-    const uint64_t nslots = 1ull << log2cap;
-    return dim3((unsigned)std::max<uint64_t>(
-        1, std::min<uint64_t>((uint64_t)std::min(std::max(1, wgs), (int)kCpMaxWgs), nslots / 256)));
-}
-
 hipError_t launch_cp_collect(const IndexEntry *tab, int log2cap, unsigned long long key, const CpList &list, CpCount *cc,
                              uint32_t *wg, CpRow *rows, uint64_t row_cap, uint32_t *err, int wgs, hipStream_t st)
 {
     if (log2cap < 8 || list.n > (uint32_t)kCpMax) return hipErrorInvalidValue;   // whole 256-slot tiles only
-    const dim3 g = cp_collect_grid(log2cap, wgs);
+    const dim3 g(walk_grid(log2cap, wgs));
     if (!rows) hipLaunchKernelGGL(cp_collect_kernel<false>, g, dim3(256), 0, st, tab, 1ull << log2cap, key, list, cc, wg,
                                   rows, row_cap, err);
     else hipLaunchKernelGGL(cp_collect_kernel<true>, g, dim3(256), 0, st, tab, 1ull << log2cap, key, list, cc, wg, rows,

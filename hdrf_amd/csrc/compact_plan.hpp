@@ -10,11 +10,12 @@
 #pragma once
 #include <stdint.h>
 
+#include "table_walk.hpp"
+
 namespace hdrf {
 
 constexpr int kCpMax = 16;                   // containers per call (HDRF_COMPACT_MAX)
 constexpr uint32_t kCpPiece = 16384;         // bytes of a container one cover / gather wave handles
-constexpr uint32_t kCpMaxWgs = 2048;         // persistent collect workgroups at most (one row-base word each)
 constexpr uint32_t kCpNoSlot = 0xffffffffu;  // CpRow::slot of the pieces after an entry's first
 
 struct CpRow {
@@ -83,7 +84,7 @@ inline uint64_t cp_map_words(uint32_t cmax) { return ((uint64_t)cmax + 31) / 32 
 // Where the pieces of one call live in the read-side scratch (ctx->d_rd), each on a 256-B boundary.
 struct CpLayout {
     uint64_t o_cnt;      // kCpMax x CpCount, + the row total
-    uint64_t o_wg;       // rows of each collect workgroup (kCpMaxWgs words)
+    uint64_t o_wg;       // rows of each collect workgroup (kWalkMaxWgs words)
     uint64_t o_lz;       // compressor 2: ClosedRec[kCpMax], the count, two work words, file lengths, segment lengths
     uint64_t o_map;      // n x map words: the cover maps
     uint64_t o_pre;      // n x map words: set bits before each word
@@ -96,7 +97,7 @@ inline CpLayout cp_layout(uint32_t n, uint32_t cmax, uint64_t rows, uint32_t lz_
     CpLayout L;
     L.o_cnt = 0;
     L.o_wg = cp_up256(L.o_cnt + (uint64_t)kCpMax * sizeof(CpCount) + 16);
-    L.o_lz = cp_up256(L.o_wg + (uint64_t)kCpMaxWgs * 4);
+    L.o_lz = cp_up256(L.o_wg + (uint64_t)kWalkMaxWgs * 4);
     // 16 B per ClosedRec, 256 B for the count and the work words, then the two length arrays
     const uint64_t lz_bytes = (uint64_t)kCpMax * 16 + 256 + cp_up256((uint64_t)kCpMax * 4) + (uint64_t)kCpMax * lz_segs * 4;
     L.o_map = cp_up256(L.o_lz + lz_bytes);

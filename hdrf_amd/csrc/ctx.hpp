@@ -341,6 +341,29 @@ inline float elapsed(hipEvent_t a, hipEvent_t b)
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
 }
 
+// Stage times of a maintenance call for its speed script (scripts/gc_speed.py, scripts/compact_speed.py):
+// when the environment variable `env` is set and not 0 (read at every call; changes no result), mark(i)
+// records event i of n on the stream and the call prints the deltas to stderr.
+struct StageTimer {
+    bool on;
+    std::vector<hipEvent_t> ev;
+    StageTimer(const char *env, int n) : on(env_int(env, 0) != 0), ev((size_t)n, nullptr)
+    {
+        for (auto &e : ev)
+            if (on && hipEventCreate(&e) != hipSuccess) on = false;
+    }
+    ~StageTimer()
+    {
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int i, hipStream_t st)
+    {
+        if (on) (void)hipEventRecord(ev[i], st);
+    }
+    float ms(int a, int b) const { return elapsed(ev[a], ev[b]); }
+};
+
 // ---- functions that cross files (callers hold the context lock) ----------------------------
 // api.hip
 // complete every batch in flight (views, reset, the node-global phases need a quiet context)

@@ -5,9 +5,10 @@
 //               then the entry's slot is set in a bitmap of one bit per table slot.  The same digest
 //               occurs many times within and across recipes; a set bit is read before it is set again,
 //               so only its first occurrences pay an atomic.
-//   gc_sweep  — a streaming pass over the table, one lane per 64-B entry.  A wave reads its 64
-//               entries as four fully coalesced 16-B loads per lane and turns them lane-major through
-//               LDS.  Live and marked: appended to the survivor rows, in the layout idx_load_kernel
+//   gc_sweep  — a streaming pass over the table, one lane per 64-B entry: table_walk.hpp's walk (the
+//               tile transposition through LDS, the prefetch and the row base of a workgroup are
+//               there, shared with compact.hip's cp_collect); this file keeps what the sweep does with
+//               an entry.  Live and marked: appended to the survivor rows, in the layout idx_load_kernel
 //               reads, so the rebuild is the restore's kernel.  Live and unmarked: dropped.  Only a
 //               live entry is ever marked, so the rows of a workgroup's tiles are counted from the
 //               bitmap alone (gc_count) and each workgroup appends from a row base of its own
@@ -19,28 +20,18 @@
 //               containers take every entry's add, and one global atomic per entry on so few
 //               addresses would serialise at the memory side; and a search through memory is eight
 //               dependent loads per tile, which was most of the sweep's time.
-#include <algorithm>
-
+// Shared parts: the sorted-list search and wave_sum_u64 (common.hpp), an entry's digest words and its
+// 11-byte value (index_entry.hpp).
 #include "gc_plan.hpp"
 #include "index_probe.hpp"
 #include "launchers.hpp"
+#include "table_walk.hpp"
 
 namespace hdrf {
 
 // containers whose ids and counters a sweep workgroup keeps in LDS: 768 x 28 B beside the 16 KiB of
 // entries is 37 KiB, so four workgroups share a CU's 160 KiB as the launch assumes (4 per CU)
 constexpr int kGcLdsCont = 768;
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 
 template <int HW>
 __global__ void __launch_bounds__(256) gc_mark_kernel(const GcJob *__restrict__ jobs, uint32_t nj, uint64_t total,
@@ -100,45 +91,26 @@ __global__ void __launch_bounds__(256) gc_sweep_kernel(const IndexEntry *__restr
                                                        uint64_t row_cap, const uint32_t *__restrict__ wg,
                                                        GcCounters *__restrict__ C)
 {
-    __shared__ uint4 s_e[4][256];                              // per wave: its 64 entries, 4 KiB
     __shared__ uint32_t s_row, s_base;                         // the workgroup's next and first survivor row
     __shared__ unsigned long long s_kb[kGcLdsCont], s_db[kGcLdsCont];
     __shared__ uint32_t s_kc[kGcLdsCont], s_dc[kGcLdsCont];
     __shared__ uint32_t s_cid[kGcLdsCont];                     // the id list's first ids: the search stays in LDS
-    const int t = (int)threadIdx.x, w = wave_id(), l = lane_id();
+    const int t = (int)threadIdx.x, l = lane_id();
     const int nlds = min(ncont, kGcLdsCont);
     for (int j = t; j < nlds; j += 256) { s_kb[j] = 0; s_db[j] = 0; s_kc[j] = 0; s_dc[j] = 0; s_cid[j] = cids[j]; }
     if (t == 0) { s_row = 0; s_base = 0; }
     __syncthreads();
-    if (dw_rows) {                                             // the rows of the workgroups before this one
-        unsigned long long before = 0;
-        for (uint32_t y = (uint32_t)t; y < blockIdx.x; y += 256u) before += wg[y];
-        before = wave_sum_u64(before);
-        if (l == 0 && before) { atomicAdd(&s_row, (uint32_t)before); atomicAdd(&s_base, (uint32_t)before); }
+    if (dw_rows) {
+        const uint32_t before = wg_row_base(wg);
+        if (l == 0 && before) { atomicAdd(&s_row, before); atomicAdd(&s_base, before); }
     }
     __syncthreads();
     unsigned long long n_ent = 0, n_kept = 0, n_drop = 0, b_kept = 0, b_drop = 0;
-    const uint64_t tstride = (uint64_t)gridDim.x * 256u;
-    // lane l's four 16-B pieces of the wave's 64 entries of a tile: piece k is bytes [(k * 64 + l) * 16, +16)
-    auto fetch = [&](uint64_t tile, uint4 r[4]) {
-        const uint8_t *wb = (const uint8_t *)(tab + tile + (uint64_t)w * 64);
-#pragma unroll
-        for (int k = 0; k < 4; k++) r[k] = ld16_nt(wb + (size_t)(k * 64 + l) * 16);
-    };
-    uint4 r[4] = {};
-    if ((uint64_t)blockIdx.x * 256u < nslots) fetch((uint64_t)blockIdx.x * 256u, r);
-    for (uint64_t tile = (uint64_t)blockIdx.x * 256u; tile < nslots; tile += tstride) {   // uniform
-#pragma unroll
-        for (int k = 0; k < 4; k++) s_e[w][k * 64 + l] = r[k];
-        __syncthreads();
-        const uint4 p0 = s_e[w][l * 4], p1 = s_e[w][l * 4 + 1], p2 = s_e[w][l * 4 + 2], p3 = s_e[w][l * 4 + 3];
-        __syncthreads();                                       // (the next tile's stores come after every read)
-        if (tile + tstride < nslots) fetch(tile + tstride, r); // in flight while this tile is classified
-        const uint64_t slot = tile + (uint64_t)t;
+    table_walk(tab, nslots, [&](uint64_t slot, uint4 p0, uint4 p1, uint4 p2, uint4 p3) {
         const unsigned long long tag = (unsigned long long)p0.x | ((unsigned long long)p0.y << 32);
         const bool live = tag_live(tag, key);
         n_ent += live ? 1u : 0u;
-        if (!mark) continue;                                   // count only (uniform)
+        if (!mark) return;                                     // count only (uniform)
         const uint32_t ncopy = p1.w, cid = p2.x, start = p2.y, stop = p2.z;
         const bool kept = live && ((mark[slot >> 5] >> (slot & 31)) & 1u);
         const unsigned long long len = (unsigned long long)stop - start;   // (as the issue defines it: stop - start)
@@ -148,12 +120,9 @@ __global__ void __launch_bounds__(256) gc_sweep_kernel(const IndexEntry *__restr
             // the container id list, sorted: its first nlds ids from LDS (eight dependent global loads
             // per tile were most of the sweep's time), the rest, if the id lies there, from memory
             const bool far = nlds < ncont && cid > s_cid[nlds - 1];
-            int lo = far ? nlds : 0, hi = far ? ncont : nlds;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if ((far ? cids[mid] : s_cid[mid]) < cid) lo = mid + 1; else hi = mid;
-            }
-            if (lo >= (far ? ncont : nlds) || (far ? cids[lo] : s_cid[lo]) != cid) {
+            const int j = find_sorted(far ? nlds : 0, far ? ncont : nlds, cid,
+                                      [&](int m) { return far ? cids[m] : s_cid[m]; });
+            if (j < 0) {
                 unknown = true;
                 if (cid < (uint32_t)kGcCidBits) {
                     uint32_t *sw = seen + (cid >> 5);
@@ -162,40 +131,28 @@ __global__ void __launch_bounds__(256) gc_sweep_kernel(const IndexEntry *__restr
                 } else {
                     atomicOr(&C->err, 1u);
                 }
-            } else if (lo < kGcLdsCont) {
-                if (kept) { atomicAdd(&s_kc[lo], 1u); atomicAdd(&s_kb[lo], len); }
-                else { atomicAdd(&s_dc[lo], 1u); atomicAdd(&s_db[lo], len); }
+            } else if (j < kGcLdsCont) {
+                if (kept) { atomicAdd(&s_kc[j], 1u); atomicAdd(&s_kb[j], len); }
+                else { atomicAdd(&s_dc[j], 1u); atomicAdd(&s_db[j], len); }
             } else {
-                if (kept) { atomicAdd(&cc[lo].kept_chunks, 1ull); atomicAdd(&cc[lo].kept_bytes, len); }
-                else { atomicAdd(&cc[lo].dropped_chunks, 1ull); atomicAdd(&cc[lo].dropped_bytes, len); }
+                if (kept) { atomicAdd(&cc[j].kept_chunks, 1ull); atomicAdd(&cc[j].kept_bytes, len); }
+                else { atomicAdd(&cc[j].dropped_chunks, 1ull); atomicAdd(&cc[j].dropped_bytes, len); }
             }
         }
         const unsigned long long um = ballot64(unknown);
         if (um && l == (int)__builtin_ctzll(um)) atomicAdd(&C->n_unknown, (uint32_t)__popcll(um));
-        if (!dw_rows) continue;                                // dry run: no survivor rows (uniform)
+        if (!dw_rows) return;                                  // dry run: no survivor rows (uniform)
         const uint32_t row = wave_append(&s_row, kept);
         if (kept && row >= row_cap) atomicOr(&C->err, 2u);     // (never: a kept entry is a distinct live digest)
         if (kept && row < row_cap) {
-            uint32_t dw[HW];                                  // the digest words the entry stands for (verify.hip vf_entry_words)
-            if (HW == 5) {
-                dw[0] = p3.z; dw[1] = p3.w;                    // dig[3..4]: digest bytes 0..7
-            } else {
-                const unsigned long long t56 = tag & kTag56;
-                dw[0] = (uint32_t)t56;
-                dw[1] = (uint32_t)(t56 >> 32) | (((ncopy >> 8) & 0xffu) << 24);
-            }
-            dw[2] = p2.w; dw[3] = p3.x; dw[4] = p3.y;          // dig[0..2]
-            if (HW == 7) { dw[HW - 2] = p3.z; dw[HW - 1] = p3.w; }
+            const uint32_t dig[5] = {p2.w, p3.x, p3.y, p3.z, p3.w};
+            uint32_t dw[HW];                                   // the digest words the entry stands for
+            entry_digest_words<HW>(tag, ncopy, dig, dw);
 #pragma unroll
             for (int k = 0; k < HW; k++) dw_rows[(size_t)row * HW + k] = dw[k];
-            uint8_t *v = val_rows + (size_t)row * 11;          // chunkMeta.getMeta, DN/chunkMeta.java:62-77
-            v[0] = (uint8_t)ncopy;
-            v[1] = (uint8_t)(cid >> 16); v[2] = (uint8_t)(cid >> 8); v[3] = (uint8_t)cid;
-            v[4] = (uint8_t)(start >> 16); v[5] = (uint8_t)(start >> 8); v[6] = (uint8_t)start;
-            v[7] = (uint8_t)(stop >> 16); v[8] = (uint8_t)(stop >> 8); v[9] = (uint8_t)stop;
-            v[10] = (uint8_t)(((start >> 20) & 0xF0) | ((stop >> 24) & 0x0F));
+            encode_value(ncopy, cid, start, stop, val_rows + (size_t)row * 11);
         }
-    }
+    });
     __syncthreads();
     if (t == 0 && s_row != s_base) atomicAdd(&C->n_rows, s_row - s_base);
     for (int j = t; j < nlds; j += 256) {                      // the workgroup's container counters leave LDS
@@ -230,8 +187,7 @@ hipError_t launch_gc_sweep(int hasher, const IndexEntry *tab, int log2cap, unsig
 {
     if (log2cap < 8 || ncont < 0) return hipErrorInvalidValue;   // whole 256-slot tiles only
     const uint64_t nslots = 1ull << log2cap;
-    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(std::max(1, wgs), (int)kGcSweepMaxWgs),
-                                                                  nslots / 256)));
+    const dim3 g(walk_grid(log2cap, wgs));
     if (dw_rows) hipLaunchKernelGGL(gc_count_kernel, g, dim3(256), 0, st, mark, nslots, wg, C);
     with_digest_words(hasher, [&](auto hw) {
         hipLaunchKernelGGL(gc_sweep_kernel<decltype(hw)::value>, g, dim3(256), 0, st, tab, nslots, key, mark, cids, ncont, cc,

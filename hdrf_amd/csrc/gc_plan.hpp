@@ -12,6 +12,8 @@
 
 #include <vector>
 
+#include "table_walk.hpp"
+
 #ifdef __HIPCC__
 #define HDRF_GC_HD __host__ __device__   // gc_mark_kernel finds its recipe with the host's function
 #else
@@ -22,7 +24,6 @@ namespace hdrf {
 
 constexpr uint32_t kGcTile = 256;            // lanes per workgroup of the mark / sweep launches
 constexpr uint32_t kGcMaxGrid = 1u << 16;    // workgroups at most: the kernels stride over the rest
-constexpr uint32_t kGcSweepMaxWgs = 2048;    // persistent sweep workgroups at most (one row-base word each)
 
 struct GcJob {
     uint64_t dig;        // device address of the recipe's digests (4-B aligned)
@@ -86,7 +87,7 @@ inline GcLayout gc_layout(uint64_t njobs, uint64_t ncont, uint64_t table_slots, 
     GcLayout L;
     L.o_cnt = 0;
     L.o_wg = 256;                                // marked slots per sweep workgroup
-    L.o_jobs = L.o_wg + gc_up256(kGcSweepMaxWgs * 4);
+    L.o_jobs = L.o_wg + gc_up256(kWalkMaxWgs * 4);
     L.o_cid = gc_up256(L.o_jobs + (njobs + 1) * sizeof(GcJob));
     L.o_ccnt = gc_up256(L.o_cid + ncont * 4);
     L.o_seen = gc_up256(L.o_ccnt + ncont * ccnt_bytes);

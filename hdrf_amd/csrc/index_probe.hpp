@@ -1,4 +1,4 @@
-// index_probe.hpp — the probe protocol of the fingerprint table (common.hpp IndexEntry), written once.
+// index_probe.hpp — the probe protocol of the fingerprint table (index_entry.hpp IndexEntry), written once.
 //
 // Every table of the project — the single-GPU index and the scratch table of the node-global front
 // (index.hip), an owner's partition of the node-global index (gx.hip), and the readers (read.hip) —
@@ -17,9 +17,11 @@
 //   };
 // (index.hip BlockOccurrence, gx.hip OwnerRecord).  Loading the digest words and addressing the slot /
 // flag arrays stay with the kernels, and so do the __restrict__ qualifiers: the helpers are inlined
-// into kernels whose parameters carry them.
+// into kernels whose parameters carry them.  The readers' lookup body (probe_read_row: find, decode,
+// locate the readable container) is here too, once for rd_lookup (read.hip) and rv_lookup (readv.hip).
 #pragma once
 #include "common.hpp"
+#include "rd_chunk.hpp"
 
 namespace hdrf {
 
@@ -137,6 +139,24 @@ __device__ __forceinline__ const IndexEntry *probe_find(const uint32_t *dw, cons
         h = (h + 1) & mask;
     }
     return nullptr;
+}
+
+// ---- find, for a reader (rd_lookup, rv_lookup): the digest's RdChunk row — where its bytes are and
+// which entry of the readable container list (cids, sorted by id) holds them; the block offset is the
+// scan's.  False when the digest is absent (the row is then empty); how a miss is reported, and whether
+// a chunk without a readable container matters, stay with the kernels.
+template <int HW>
+__device__ __forceinline__ bool probe_read_row(const uint32_t *dw, const IndexEntry *tab, int log2cap,
+                                               unsigned long long key, const uint32_t *cids, int ncont, RdChunk &r)
+{
+    r.slot = kRdNoSlot; r.start = 0; r.len = 0; r.off = 0;
+    const IndexEntry *e = probe_find<HW>(dw, tab, log2cap, key);
+    if (!e) return false;
+    r.start = e->start;
+    r.len = e->stop - e->start;                              // chunkMeta.length = blockStop - blockStart
+    const int j = find_cid(cids, ncont, e->cid);
+    if (j >= 0) r.slot = (uint32_t)j;
+    return true;
 }
 
 // ---- claim the first empty slot of a tag's probe sequence (restore: digests are unique, nothing is

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "rd_chunk.hpp"
 
 namespace hdrf {
 
@@ -237,22 +238,20 @@ hipError_t launch_lz4(const ClosedRec *closed, const uint32_t *nclosed, int clos
                       const uint8_t *arena, uint8_t *carena, uint64_t cslot, uint32_t *seg_clen, uint32_t *file_len,
                       uint32_t *work, hipStream_t st);
 // read side (read.hip): lookup + scan (gather = false), then the copy (gather = true)
-size_t rd_chunk_bytes();
 hipError_t launch_gx_locate(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                             unsigned long long key, int G, int rank, uint32_t *loc, int *err, hipStream_t st);
-hipError_t launch_rd_gather(const void *chunks, int n, const uint64_t *bases, uint8_t *out, hipStream_t st);
+hipError_t launch_rd_gather(const RdChunk *chunks, int n, const uint64_t *bases, uint8_t *out, hipStream_t st);
 hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                               unsigned long long key, const uint32_t *cids, const uint64_t *bases, int ncont,
-                              void *chunks, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather);
+                              RdChunk *chunks, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather);
 // batched, ranged reads (readv.hip): nreq requests (ReadDesc, read_plan.hpp) with nrows chunk rows
-// (rv_chunk_bytes each, the RdChunk layout) and ntiles output tiles of T bytes in all.  Lookup, scan
+// (RdChunk, rd_chunk.hpp) and ntiles output tiles of T bytes in all.  Lookup, scan
 // and gather are enqueued back to back; status[r] != 0 (cleared by the caller) tells which requests
 // failed (kReadNotFound / kReadDevice) and wrote nothing.
 struct ReadDesc;
-size_t rv_chunk_bytes();
 hipError_t launch_readv(int hasher, const ReadDesc *req, int nreq, uint32_t nrows, uint32_t ntiles, uint32_t T,
                         const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *cids,
-                        const uint64_t *bases, int ncont, void *rows, int *status, hipStream_t st);
+                        const uint64_t *bases, int ncont, RdChunk *rows, int *status, hipStream_t st);
 // fingerprint scrub / verified reads (verify.hip).  Counters of one table slice (scrub) or one
 // rebuilt block (verified read), zeroed by the caller before the launches.
 struct VfCounters {
@@ -284,7 +283,7 @@ hipError_t launch_vf_hash_items(int hasher, const void *items, const IndexEntry 
                                 hipStream_t st);
 // hash the n chunks (RdChunk rows of launch_reconstruct) of a rebuilt block of block_bytes bytes
 // against the recipe digests dig
-hipError_t launch_vf_hash_block(int hasher, const void *chunks, int n, const uint32_t *dig, const uint8_t *block,
+hipError_t launch_vf_hash_block(int hasher, const RdChunk *chunks, int n, const uint32_t *dig, const uint8_t *block,
                                 uint64_t block_bytes, VfCounters *C, int wgs, hipStream_t st);
 hipError_t launch_vf_rows(int hasher, const uint32_t *bad, uint32_t from, uint32_t n, const IndexEntry *tab,
                           uint64_t slot0, VfBadRow *out, hipStream_t st);
@@ -310,7 +309,7 @@ hipError_t launch_gc_mark(int hasher, const GcJob *jobs, uint32_t nj, uint64_t t
 // launch_index_load reads (dw_rows: digest words, val_rows: 11-byte values; row_cap rows, none when
 // dw_rows is null); live and unmarked: dropped.  Both add to cc[] of their container (cids: sorted, ncont
 // ids); an id outside the list is set in `seen` (2^24 bits) and counted in n_unknown instead.
-// wg (kGcSweepMaxWgs words, needed with dw_rows): the marked slots of each workgroup's tiles, counted
+// wg (kWalkMaxWgs words, needed with dw_rows): the marked slots of each workgroup's tiles, counted
 // first, give every workgroup the first row of its own.
 // mark == nullptr: only C->entries is counted (the check after a rebuild).
 hipError_t launch_gc_sweep(int hasher, const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *mark,

@@ -7,10 +7,12 @@
 // DN/chunkMeta.java:35-60), and threadedConstructor copies container[start, stop) to
 // data[bbStart, bbStop) (:474-531).
 //
-//   rd_lookup — one lane per chunk: probe the index (index_probe.hpp probe_find), decode
-//               (container id, start, stop), and the readable copy of the container (an arena
+//   rd_lookup — one lane per chunk: its RdChunk row (rd_chunk.hpp) from index_probe.hpp's
+//               probe_read_row, the lookup body shared with rv_lookup: probe the index, decode
+//               (container id, start, stop), and find the readable copy of the container (an arena
 //               slot, or a container loaded back from its file with hdrf_container_load)
 //   rd_scan   — one workgroup: exclusive prefix of the chunk lengths (block offsets) + total
+//               (common.hpp wg1024_excl_scan)
 //   rd_gather — one wave per chunk: 16-B-per-lane copy arena -> output block
 //   gx_locate — node-global contexts: the owner's lookup of the digests it owns (location +
 //               placing rank); each rank then gathers the chunks it placed (hdrf_gx_read_*)
@@ -18,12 +20,6 @@
 #include "launchers.hpp"
 
 namespace hdrf {
-
-struct RdChunk {
-    uint32_t slot;       // index of the container in the readable list (0xffffffff: missing)
-    uint32_t start, len;
-    uint32_t off;        // offset in the rebuilt block
-};
 
 template <int HW>
 __global__ void __launch_bounds__(256) rd_lookup_kernel(const uint32_t *__restrict__ dig, int n,
@@ -37,19 +33,8 @@ __global__ void __launch_bounds__(256) rd_lookup_kernel(const uint32_t *__restri
 #pragma unroll
     for (int i = 0; i < HW; i++) dw[i] = dig[(size_t)k * HW + i];
     RdChunk r;
-    r.slot = 0xffffffffu; r.start = 0; r.len = 0; r.off = 0;
-    const IndexEntry *e = probe_find<HW>(dw, tab, log2cap, tag_mask);
-    if (e) {
-        r.start = e->start;
-        r.len = e->stop - e->start;                    // chunkMeta.length = blockStop - blockStart
-        int lo = 0, hi = ncont;                        // readable container list, sorted by id
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cids[mid] < e->cid) lo = mid + 1; else hi = mid;
-        }
-        if (lo < ncont && cids[lo] == e->cid) r.slot = (uint32_t)lo;
-    }
-    if (!e || (r.slot == 0xffffffffu && r.len != 0)) atomicOr(err, 1);   // empty chunks need no container
+    const bool found = probe_read_row<HW>(dw, tab, log2cap, tag_mask, cids, ncont, r);
+    if (!found || (r.slot == kRdNoSlot && r.len != 0)) atomicOr(err, 1);   // empty chunks need no container
     out[k] = r;
 }
 
@@ -81,26 +66,15 @@ __global__ void __launch_bounds__(256) gx_locate_kernel(const uint32_t *__restri
 __global__ void __launch_bounds__(1024) rd_scan_kernel(RdChunk *__restrict__ c, int n, uint64_t *__restrict__ total)
 {
     __shared__ uint32_t s_w[16];
-    __shared__ uint64_t s_carry;
+    __shared__ unsigned long long s_carry;
     const int t = threadIdx.x;
     if (t == 0) s_carry = 0;
     __syncthreads();
     for (int base = 0; base < n; base += 1024) {
         const int k = base + t;
-        const uint32_t v = k < n ? c[k].len : 0u;
-        const uint32_t incl = wave_incl_scan(v);
-        if (lane_id() == 63) s_w[t >> 6] = incl;
-        __syncthreads();
-        uint32_t add = 0, tot = 0;
-        for (int i = 0; i < 16; i++) {
-            if (i < (t >> 6)) add += s_w[i];
-            tot += s_w[i];
-        }
-        const uint64_t carry = s_carry;
-        if (k < n) c[k].off = (uint32_t)(carry + add + incl - v);
-        __syncthreads();
-        if (t == 0) s_carry = carry + tot;
-        __syncthreads();
+        wg1024_excl_scan(k < n ? c[k].len : 0u, s_w, &s_carry, [&](unsigned long long off) {
+            if (k < n) c[k].off = (uint32_t)off;
+        });
     }
     if (t == 0) *total = s_carry;
 }
@@ -112,7 +86,9 @@ __global__ void __launch_bounds__(256) rd_gather_kernel(const RdChunk *__restric
     const int k = blockIdx.x * 4 + wave_id();
     if (k >= n) return;
     const RdChunk r = c[k];
-    if (r.slot == 0xffffffffu) return;
+    if (r.slot == kRdNoSlot) return;
+    // wave_copy<false> (bytes.hpp) without its four-in-flight loop: measured, on wave_copy the whole-block
+    // read of ~1 KB chunks ran 1-2 % slower (medians 5.30 against 5.23 ms, profiles/maint_refactor_ab_20261021.txt)
     const uint8_t *src = (const uint8_t *)(uintptr_t)bases[r.slot] + r.start;
     uint8_t *dst = out + r.off;
     const int l = lane_id();
@@ -132,9 +108,8 @@ __global__ void __launch_bounds__(256) rd_gather_kernel(const RdChunk *__restric
 
 hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                               unsigned long long tag_mask, const uint32_t *cids, const uint64_t *bases, int ncont,
-                              void *chunks, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather)
+                              RdChunk *c, uint64_t *total, uint8_t *out, int *err, hipStream_t st, bool gather)
 {
-    RdChunk *c = (RdChunk *)chunks;
     if (n <= 0) return hipSuccess;
     if (!gather) {
         const dim3 g((n + 255) / 256);
@@ -149,8 +124,6 @@ hipError_t launch_reconstruct(int hasher, const uint32_t *dig, int n, const Inde
     return hipGetLastError();
 }
 
-size_t rd_chunk_bytes() { return sizeof(RdChunk); }
-
 hipError_t launch_gx_locate(int hasher, const uint32_t *dig, int n, const IndexEntry *tab, int log2cap,
                             unsigned long long tag_mask, int G, int rank, uint32_t *loc, int *err, hipStream_t st)
 {
@@ -164,10 +137,10 @@ hipError_t launch_gx_locate(int hasher, const uint32_t *dig, int n, const IndexE
 }
 
 // gather a host-built chunk list (RdChunk {base index, start, len, off}) into out
-hipError_t launch_rd_gather(const void *chunks, int n, const uint64_t *bases, uint8_t *out, hipStream_t st)
+hipError_t launch_rd_gather(const RdChunk *chunks, int n, const uint64_t *bases, uint8_t *out, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rd_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, st, (const RdChunk *)chunks, n, bases, out);
+    hipLaunchKernelGGL(rd_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, st, chunks, n, bases, out);
     return hipGetLastError();
 }
 

@@ -5,10 +5,10 @@
 // whole block and seeking into it (DN/BlockSender.java:612-619); here only the chunks that overlap
 // the range are copied.  The requests of a call are described by ReadDesc rows (read_plan.hpp).
 //
-//   rv_lookup — one lane per (request, chunk) over all requests' digests: probe the index
-//               (index_probe.hpp probe_find) and find the readable copy of the container; the same
-//               RdChunk rows as rd_lookup (read.hip).  An absent digest fails its request.
-//   rv_scan   — one workgroup per request: block offsets of its chunks (rd_scan's segmented body),
+//   rv_lookup — one lane per (request, chunk) over all requests' digests: the chunk's RdChunk row
+//               (rd_chunk.hpp) from index_probe.hpp's probe_read_row, the lookup body shared with
+//               rd_lookup (read.hip).  An absent digest fails its request.
+//   rv_scan   — one workgroup per request: block offsets of its chunks (common.hpp wg1024_excl_scan),
 //               the total against the recipe size, and the readable-container check for the chunks
 //               that overlap the request's range
 //   rv_gather — partitioned by OUTPUT: one wave per tile of T output bytes (read_plan.hpp).  The
@@ -23,30 +23,11 @@
 
 namespace hdrf {
 
-struct RvChunk {         // RdChunk of read.hip, field for field
-    uint32_t slot;       // index of the container in the readable list (0xffffffff: missing)
-    uint32_t start, len;
-    uint32_t off;        // offset in the block
-};
-static_assert(sizeof(RvChunk) == 16, "RdChunk layout");
-
-// the last r in [0, n) with key(r) <= v (key ascending, key(0) <= v)
-template <class K>
-__device__ __forceinline__ uint32_t last_le(uint32_t n, uint32_t v, K key)
-{
-    uint32_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 template <int HW>
 __global__ void __launch_bounds__(256) rv_lookup_kernel(const ReadDesc *__restrict__ req, uint32_t nreq, uint32_t nrows,
                                                         const IndexEntry *__restrict__ tab, int log2cap,
                                                         unsigned long long tag_mask, const uint32_t *__restrict__ cids,
-                                                        int ncont, RvChunk *__restrict__ rows, int *__restrict__ status)
+                                                        int ncont, RdChunk *__restrict__ rows, int *__restrict__ status)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= nrows) return;
@@ -56,33 +37,21 @@ __global__ void __launch_bounds__(256) rv_lookup_kernel(const ReadDesc *__restri
     uint32_t dw[HW];
 #pragma unroll
     for (int k = 0; k < HW; k++) dw[k] = dig[k];
-    RvChunk c;
-    c.slot = 0xffffffffu; c.start = 0; c.len = 0; c.off = 0;
-    const IndexEntry *e = probe_find<HW>(dw, tab, log2cap, tag_mask);
-    if (e) {
-        c.start = e->start;
-        c.len = e->stop - e->start;                    // chunkMeta.length = blockStop - blockStart
-        int lo = 0, hi = ncont;                        // readable container list, sorted by id
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cids[mid] < e->cid) lo = mid + 1; else hi = mid;
-        }
-        if (lo < ncont && cids[lo] == e->cid) c.slot = (uint32_t)lo;
-    } else {
+    RdChunk c;
+    if (!probe_read_row<HW>(dw, tab, log2cap, tag_mask, cids, ncont, c))
         atomicOr(status + r, kReadNotFound);           // no offsets without its length
-    }
     rows[i] = c;
 }
 
 // grid nreq x 1024: off[k] = sum of len[0..k) over the request's rows; the total must be the recipe
 // size; a chunk with bytes, no readable container and an overlap with the range fails the request
-__global__ void __launch_bounds__(1024) rv_scan_kernel(const ReadDesc *__restrict__ req, RvChunk *__restrict__ rows,
+__global__ void __launch_bounds__(1024) rv_scan_kernel(const ReadDesc *__restrict__ req, RdChunk *__restrict__ rows,
                                                        int *__restrict__ status)
 {
     __shared__ uint32_t s_w[16];
-    __shared__ uint64_t s_carry;
+    __shared__ unsigned long long s_carry;
     const ReadDesc q = req[blockIdx.x];
-    RvChunk *c = rows + q.row0;
+    RdChunk *c = rows + q.row0;
     const int n = (int)q.n;
     const int t = threadIdx.x;
     const uint64_t r0 = q.off, r1 = (uint64_t)q.off + q.len;
@@ -92,23 +61,12 @@ __global__ void __launch_bounds__(1024) rv_scan_kernel(const ReadDesc *__restric
     for (int base = 0; base < n; base += 1024) {
         const int k = base + t;
         const uint32_t v = k < n ? c[k].len : 0u;
-        const uint32_t incl = wave_incl_scan(v);
-        if (lane_id() == 63) s_w[t >> 6] = incl;
-        __syncthreads();
-        uint32_t add = 0, tot = 0;
-        for (int i = 0; i < 16; i++) {
-            if (i < (t >> 6)) add += s_w[i];
-            tot += s_w[i];
-        }
-        const uint64_t carry = s_carry;
-        const uint64_t off = carry + add + incl - v;
-        if (k < n) {
-            c[k].off = (uint32_t)off;
-            miss |= v != 0u && c[k].slot == 0xffffffffu && off < r1 && off + v > r0;
-        }
-        __syncthreads();
-        if (t == 0) s_carry = carry + tot;
-        __syncthreads();
+        wg1024_excl_scan(v, s_w, &s_carry, [&](uint64_t off) {
+            if (k < n) {
+                c[k].off = (uint32_t)off;
+                miss |= v != 0u && c[k].slot == kRdNoSlot && off < r1 && off + v > r0;
+            }
+        });
     }
     if (miss) atomicOr(status + blockIdx.x, kReadNotFound);
     if (t == 0 && s_carry != q.size) atomicOr(status + blockIdx.x, kReadDevice);
@@ -117,7 +75,7 @@ __global__ void __launch_bounds__(1024) rv_scan_kernel(const ReadDesc *__restric
 // grid ceil(ntiles / 4) x 256: wave w of the workgroup fills output tile 4 * blockIdx.x + w
 __global__ void __launch_bounds__(256) rv_gather_kernel(const ReadDesc *__restrict__ req, uint32_t nreq,
                                                         const int *__restrict__ status,
-                                                        const RvChunk *__restrict__ rows,
+                                                        const RdChunk *__restrict__ rows,
                                                         const uint64_t *__restrict__ bases, uint32_t ntiles, uint32_t T)
 {
     const uint32_t tile = blockIdx.x * 4u + (uint32_t)wave_id();
@@ -128,31 +86,28 @@ __global__ void __launch_bounds__(256) rv_gather_kernel(const ReadDesc *__restri
     const ReadDesc q = req[r];
     uint64_t t0, t1;
     read_tile_span(q.out, q.len, T, tile - q.tile0, &t0, &t1);
-    const RvChunk *c = rows + q.row0;
+    const RdChunk *c = rows + q.row0;
     uint64_t pos = q.off + t0;                         // block offsets [pos, end) land in this tile
     const uint64_t end = q.off + t1;
     // empty chunks share their offset with the next one: the last match holds the byte at pos
     uint32_t k = rdfirst(last_le(q.n, (uint32_t)pos, [&](uint32_t m) { return c[m].off; }));
     uint8_t *out = (uint8_t *)(uintptr_t)q.out;
     for (; pos < end && k < q.n; k++) {
-        const RvChunk ch = c[k];
+        const RdChunk ch = c[k];
         const uint64_t cend = (uint64_t)ch.off + ch.len;
         if (cend <= pos) continue;
         const uint64_t pe = cend < end ? cend : end;
-        if (ch.slot != 0xffffffffu)                    // (rv_scan failed the request otherwise)
+        if (ch.slot != kRdNoSlot)                      // (rv_scan failed the request otherwise)
             wave_copy(out + (pos - q.off), (const uint8_t *)(uintptr_t)bases[ch.slot] + ch.start + (pos - ch.off),
-                      (int)(pe - pos));
+                      (uint32_t)(pe - pos));
         pos = pe;
     }
 }
 
-size_t rv_chunk_bytes() { return sizeof(RvChunk); }
-
 hipError_t launch_readv(int hasher, const ReadDesc *req, int nreq, uint32_t nrows, uint32_t ntiles, uint32_t T,
                         const IndexEntry *tab, int log2cap, unsigned long long tag_mask, const uint32_t *cids,
-                        const uint64_t *bases, int ncont, void *rows, int *status, hipStream_t st)
+                        const uint64_t *bases, int ncont, RdChunk *c, int *status, hipStream_t st)
 {
-    RvChunk *c = (RvChunk *)rows;
     if (nreq <= 0) return hipSuccess;
     if (nrows) {
         with_digest_words(hasher, [&](auto hw) {

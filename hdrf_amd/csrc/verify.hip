@@ -13,9 +13,9 @@
 //                two blocks per iteration from one 132-B window) and, when it finishes, takes the
 //                next item from the wave's register pool of 64 items reserved from a global
 //                cursor, so a 1,000,000-B forced-cut chunk never leaves 63 lanes idle.  Scrub: items from
-//                vf_collect, expected digest from the table entry.  Verified read: the items are
-//                the RdChunk rows of the lookup over the rebuilt block, expected digest from the
-//                recipe.
+//                vf_collect, expected digest from the table entry (index_entry.hpp
+//                entry_digest_words).  Verified read: the items are the RdChunk rows (rd_chunk.hpp) of
+//                the lookup over the rebuilt block, expected digest from the recipe.
 //   vf_rows    — bad-list rows (table slot, reason) -> hdrf_bad_chunk records
 #include <algorithm>
 
@@ -32,10 +32,6 @@ struct VfItem {              // one chunk to hash
     uint32_t start, len;
 };
 static_assert(sizeof(VfItem) == 16, "VfItem is one 16-B load");
-
-struct RdChunkV {            // read.hip RdChunk (rd_chunk_bytes() == 16, checked by the launcher)
-    uint32_t slot, start, len, off;
-};
 
 // Persistent workgroups: workgroup x takes the 256-slot tiles x, x + gridDim.x, ... of the slice.
 // Items are compacted into an LDS batch first (ballot + mbcnt per wave, an LDS counter per
@@ -77,14 +73,10 @@ __global__ void __launch_bounds__(256) vf_collect_kernel(const IndexEntry *__res
         int kind = 0;                                          // 1 skipped, 2 bad range, 3 item
         uint32_t ridx = 0;
         if (live) {
-            int lo = 0, hi = ncont;                            // readable container list, sorted by id
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (cids[mid] < cid) lo = mid + 1; else hi = mid;
-            }
-            if (lo >= ncont || cids[lo] != cid) kind = 1;
-            else if (start > stop || stop > valid[lo]) kind = 2;
-            else { kind = 3; ridx = (uint32_t)lo; }
+            const int j = find_cid(cids, ncont, cid);
+            if (j < 0) kind = 1;
+            else if (start > stop || stop > valid[j]) kind = 2;
+            else { kind = 3; ridx = (uint32_t)j; }
         }
         n_ent += live ? 1u : 0u;
         n_skip += kind == 1 ? 1u : 0u;
@@ -112,31 +104,13 @@ __global__ void __launch_bounds__(256) vf_collect_kernel(const IndexEntry *__res
     }
 }
 
-// the digest words (little-endian loads of the digest bytes) an index entry stands for: SHA-1 keeps
-// bytes 0..7 in dig[3..4]; SHA-224 keeps bytes 0..6 in the tag and byte 7 in ncopy bits 8..15
-template <int HW>
-__device__ __forceinline__ void vf_entry_words(const IndexEntry &e, uint32_t dw[HW])
-{
-    if (HW == 5) {
-        dw[0] = e.dig[3]; dw[1] = e.dig[4];
-#pragma unroll
-        for (int i = 2; i < HW; i++) dw[i] = e.dig[i - 2];
-    } else {
-        const unsigned long long t = e.tag & kTag56;
-        dw[0] = (uint32_t)t;
-        dw[1] = (uint32_t)(t >> 32) | (((e.ncopy >> 8) & 0xffu) << 24);
-#pragma unroll
-        for (int i = 2; i < HW; i++) dw[i] = e.dig[i - 2];
-    }
-}
-
 // READ = false (scrub): items[0 .. *C.n_items) from vf_collect over slots slot0 + item.slot of tab;
 // base / readable of an item = bases / allocs[item.ridx].
 // READ = true (verified read): item k = chunk k of the rebuilt block: chunks[k].len bytes at
 // block_base + block_mis + chunks[k].off (block_base 4-B aligned, block_readable bytes readable from
 // it), expected digest dig[k * HW ..]; the lowest failing k lands in C.first_bad_inv (as ~k).
 template <int HW, bool READ>
-__global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__ items, const RdChunkV *__restrict__ chunks,
+__global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__ items, const RdChunk *__restrict__ chunks,
                                                       uint32_t n_read, const uint32_t *__restrict__ dig,
                                                       const IndexEntry *__restrict__ tab, uint64_t slot0,
                                                       const uint64_t *__restrict__ bases,
@@ -165,7 +139,8 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
 #pragma unroll
                 for (int i = 0; i < HW; i++) want[i] = dig[(size_t)k * HW + i];
             } else {
-                vf_entry_words<HW>(tab[slot0 + k], want);
+                const IndexEntry &e = tab[slot0 + k];
+                entry_digest_words<HW>(e.tag, e.ncopy, e.dig, want);
             }
 #pragma unroll
             for (int i = 0; i < HW; i++) mism |= __builtin_bswap32(st[i]) != want[i];
@@ -197,7 +172,7 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
                 head = 0;
                 if (l < cntP) {
                     if (READ) {
-                        const RdChunkV c = chunks[kbP + l];
+                        const RdChunk c = chunks[kbP + l];
                         p0 = kbP + (uint32_t)l; p1 = 0u; p2 = c.off + block_mis; p3 = c.len;
                     } else {
                         const VfItem it = items[kbP + l];
@@ -231,13 +206,8 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
         if (active) sha_iter<HW>(base, readable, s0, len, T, nb, bi, st);   // sha_core.hpp
     }
     // hashed bytes and items: one atomic pair per wave
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)bytes, d, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(bytes >> 32), d, 64);
-        bytes += ((unsigned long long)hi << 32) | lo;
-        done_n += (uint32_t)__shfl_xor((int)done_n, d, 64);
-    }
+    bytes = wave_sum_u64(bytes);
+    done_n = (uint32_t)wave_sum_u64(done_n);
     if (lane_id() == 0 && done_n) {
         atomicAdd(&C->bytes, bytes);
         atomicAdd(&C->checked, done_n);
@@ -255,7 +225,7 @@ __global__ void __launch_bounds__(256) vf_rows_kernel(const uint32_t *__restrict
     const IndexEntry &e = tab[slot0 + bad[2 * (size_t)(from + i)]];
     VfBadRow r;
     uint32_t dw[HW];
-    vf_entry_words<HW>(e, dw);
+    entry_digest_words<HW>(e.tag, e.ncopy, e.dig, dw);
 #pragma unroll
     for (int j = 0; j < 7; j++) r.dig[j] = j < HW ? dw[j] : 0u;
     r.cid = e.cid; r.start = e.start; r.stop = e.stop;
@@ -285,16 +255,15 @@ hipError_t launch_vf_hash_items(int hasher, const void *items, const IndexEntry 
     return hipGetLastError();
 }
 
-hipError_t launch_vf_hash_block(int hasher, const void *chunks, int n, const uint32_t *dig, const uint8_t *block,
+hipError_t launch_vf_hash_block(int hasher, const RdChunk *chunks, int n, const uint32_t *dig, const uint8_t *block,
                                 uint64_t block_bytes, VfCounters *C, int wgs, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    if (rd_chunk_bytes() != sizeof(RdChunkV)) return hipErrorInvalidValue;
     // load_win fetches dwords at base + (pos & ~3): the base goes down to a dword, the rest into pos
     const uint32_t mis = (uint32_t)((uintptr_t)block & 3u);
     const dim3 g(std::max(1, std::min(wgs, (n + 255) / 256)));
     with_digest_words(hasher, [&](auto hw) {
-        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, true>), g, dim3(256), 0, st, nullptr, (const RdChunkV *)chunks,
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, true>), g, dim3(256), 0, st, nullptr, chunks,
                            (uint32_t)n, dig, nullptr, 0ull, nullptr, nullptr, block - mis, mis, block_bytes + mis, nullptr, C);
     });
     return hipGetLastError();

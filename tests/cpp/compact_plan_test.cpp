@@ -101,7 +101,7 @@ int main()
                 for (int i = 0; i < 7; i++) CHECK(o[i] % 256 == 0);
                 for (int i = 0; i + 1 < 7; i++) CHECK(o[i] < o[i + 1]);
                 CHECK(L.o_wg - L.o_cnt >= kCpMax * sizeof(CpCount) + 4);       // counters + the error word
-                CHECK(L.o_lz - L.o_wg >= kCpMaxWgs * 4 && L.o_lz - L.o_wg >= kCpMax * 8);   // (the bases reuse it)
+                CHECK(L.o_lz - L.o_wg >= kWalkMaxWgs * 4 && L.o_lz - L.o_wg >= kCpMax * 8);   // (the bases reuse it)
                 CHECK(kCpLzCount >= kCpMax * 16 && kCpLzWork >= kCpLzCount + 4 && kCpLzFileLen >= kCpLzWork + 8);
                 CHECK(cp_lz_seglen() >= kCpLzFileLen + kCpMax * 4);
                 CHECK(L.o_map - L.o_lz >= cp_lz_seglen() + (uint64_t)kCpMax * segs * 4);

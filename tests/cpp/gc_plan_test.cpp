@@ -108,7 +108,7 @@ static int test_rows_and_layout()
                     for (uint32_t hw : {5u, 7u}) {
                         const GcLayout L = gc_layout(nj, nc, slots, rows, hw, 32);
                         const uint64_t o[] = {L.o_cnt, L.o_wg, L.o_jobs, L.o_cid, L.o_ccnt, L.o_seen, L.o_mark, L.o_dw, L.o_val};
-                        const uint64_t need[] = {256, kGcSweepMaxWgs * 4, (nj + 1) * sizeof(GcJob), nc * 4, nc * 32,
+                        const uint64_t need[] = {256, kWalkMaxWgs * 4, (nj + 1) * sizeof(GcJob), nc * 4, nc * 32,
                                                  kGcCidBits / 8, slots / 8, rows * hw * 4, rows * 11};
                         for (int i = 0; i < 9; i++) {
                             CHECK(o[i] % 256 == 0);

@@ -40,6 +40,20 @@ def test_null_context_is_invalid():
     assert L.hdrf_reconstruct_block_verified(None, 1, None, 0, ctypes.byref(bad)) == -1
 
 
+def test_entry_codec_under_asan_and_ubsan(tmp_path):
+    """tests/cpp/entry_codec_test.cpp: an entry's digest packing against its inverse for both hashers, and
+    the 11-byte value against chunkMeta.getMeta byte by byte, as a plain program built with
+    -fsanitize=address,undefined."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "entry_codec_test")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", os.path.join(root, "tests", "cpp", "entry_codec_test.cpp"), "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and "PASS" in r.stdout
+
+
 # ---- helpers ----------------------------------------------------------------------------------
 def enc_value(ncopy, cid, start, stop):
     """chunkMeta.getMeta: the 11-byte index value."""
