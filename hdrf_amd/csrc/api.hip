@@ -283,6 +283,7 @@ static int init_state(hdrf_ctx *ctx, bool fresh)
     reset_host(ctx);
     for (auto &S : ctx->sl) S.recipe_pending = S.gen_reset = false;
     ctx->last_nblocks = 0;
+    ctx->probe_stale = false;
     ctx->gx_nfront = ctx->gx_nfwait = ctx->gx_nback = 0;
     ctx->gx_bphase = 0;
     ctx->gx_dscan = ctx->gx_scanned = 0;
@@ -835,6 +836,7 @@ int host::complete_slot(hdrf_ctx *ctx, int si, bool timed)
     }
     ctx->res = si;
     ctx->last_nblocks = nblocks;
+    ctx->probe_stale = false;
     ctx->h_alloc = *S.h_alloc;
     const int herr = *S.h_err;
     if (herr) {

@@ -62,6 +62,10 @@ extern "C" int hdrf_probe_stats(hdrf_ctx *ctx, int64_t *probe_sum, int64_t *prob
     if (int rc = drain(ctx)) return rc;
     Slot &S = ctx->sl[ctx->res];
     if (ctx->last_nblocks < 1) return set_err(ctx, HDRF_E_INVAL, "no completed batch");
+    if (ctx->probe_stale) {                              // the batch's slots are those of the table before a resize
+        *probe_sum = *probe_max = *chunks = 0;
+        return 0;
+    }
     unsigned long long *d = nullptr;
     HIPCK(hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
     unsigned long long h[3] = {0, 0, 0};

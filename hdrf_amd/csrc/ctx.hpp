@@ -2,7 +2,7 @@
 // units share.  Internal: included only by the api*.hip files (api.hip core and batch pipeline,
 // api_rx.hip packet receive, api_stream.hip stream codecs, api_gx.hip node-global phases,
 // api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub, api_gc.hip block deletion and
-// index garbage collection, api_compact.hip container compaction); each of them names in its header comment
+// index garbage collection, api_compact.hip container compaction, api_resize.hip online table resize); each of them names in its header comment
 // the context state it may write.  Everything here but hdrf_ctx itself lives in hdrf::host, hidden
 // from the library's dynamic symbols.
 #pragma once
@@ -181,6 +181,8 @@ struct hdrf_ctx {
     uint32_t scratch_epoch[kSlots] = {};             // node-global: generation of each scratch table
     int have_alloc = 0;
     int last_nblocks = 0;
+    bool probe_stale = false;                        // hdrf_index_resize ran since the last completed batch: its
+                                                     // slot numbers (Slot::d_slot) are the old table's (hdrf_probe_stats)
     AllocState h_alloc{};
     std::map<uint32_t, ContainerInfo> containers;   // container id -> arena slot
     std::map<uint32_t, uint32_t> slot_owner;         // arena slot -> container id

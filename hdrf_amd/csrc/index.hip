@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(256) idx_clear_kernel(u32x4 *__restrict__ p, u
         __builtin_nontemporal_store(z, p + i + 3 * stride);
     }
     for (; i < n16; i += stride) __builtin_nontemporal_store(z, p + i);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (alloc && blockIdx.x == 0 && threadIdx.x == 0) {
         if (ring_per)
             for (int t = 0; t < 4; t++) {
                 const uint32_t base = (uint32_t)t * ring_per, s = alloc->slot[t];

@@ -96,7 +96,8 @@ hipError_t launch_crc32_pieces(const uint8_t *data, int64_t n, const CrcOp &op1k
 hipError_t launch_index_probe(int hasher, const BlockState *bst, int nblocks, int cap_blk, const uint32_t *digests,
                               const uint32_t *slot, int log2cap, unsigned long long key,
                               unsigned long long *stats, hipStream_t st);
-// (log2cap < 0: only the allocator seed; a reset that bumps the index epoch)
+// (log2cap < 0: only the allocator seed; a reset that bumps the index epoch.  d_alloc == nullptr: only
+//  the table; the device allocator is neither read nor written: hdrf_index_resize's new table)
 hipError_t launch_index_clear(IndexEntry *tab, int log2cap, AllocState *d_alloc, const AllocState &a, hipStream_t st,
                               uint32_t ring_per = 0);
 hipError_t launch_index(int hasher, const BlockState *bst, int nblocks, int cap_blk, const uint32_t *offsets,
@@ -334,6 +335,11 @@ hipError_t launch_cp_gather(const CpRow *rows, uint32_t nrows, uint32_t go, cons
 // the new start / stop of the entries of the containers in `go`
 hipError_t launch_cp_rewrite(const CpRow *rows, uint32_t nrows, uint32_t go, const uint32_t *maps, const uint32_t *pres,
                              uint64_t map_words, IndexEntry *tab, hipStream_t st);
+// online table resize (resize.hip; the checks, the grid and the byte counts are resize_plan.hpp's): every
+// live entry of old_tab (2^old_log2 slots) claims a slot of new_tab (2^new_log2 slots, cleared by the
+// caller) and is stored there verbatim.  *err (cleared by the caller) |= 1: new_tab was full.
+hipError_t launch_index_rehash(const IndexEntry *old_tab, int old_log2, unsigned long long key, IndexEntry *new_tab,
+                               int new_log2, uint32_t *err, int n_cu, hipStream_t st);
 hipError_t launch_corpus(uint8_t *dev, const uint32_t *d_roots, int64_t nblocks, int64_t spb, int64_t seg_bytes,
                          uint64_t seed, int mixed, hipStream_t st);
 

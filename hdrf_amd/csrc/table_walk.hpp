@@ -1,5 +1,5 @@
-// table_walk.hpp — the streaming pass over the whole index table that gc_sweep (gc.hip) and cp_collect
-// (compact.hip) share: persistent workgroups of 256 lanes, workgroup x takes the 256-slot tiles x,
+// table_walk.hpp — the streaming pass over the whole index table that gc_sweep (gc.hip), cp_collect
+// (compact.hip) and ix_rehash (resize.hip) share: persistent workgroups of 256 lanes, workgroup x takes the 256-slot tiles x,
 // x + gridDim.x, ... of the table, one lane per 64-B entry.  A pass that appends rows runs after a
 // counting pass with the same grid, which leaves in wg[x] the rows workgroup x will write: every
 // workgroup then appends from a row base of its own through an LDS counter (one

@@ -40,6 +40,7 @@ EXPORTS = [
     "hdrf_read_batch", "hdrf_read_range",
     "hdrf_block_delete", "hdrf_gc",
     "hdrf_compact",
+    "hdrf_index_info_get", "hdrf_index_resize",
     "hdrf_batch_seg_trace",
 ]
 
@@ -122,6 +123,11 @@ class CompactRow(ctypes.Structure):         # hdrf_compact_row (56 B)
     _fields_ = [("id", ctypes.c_uint32), ("status", ctypes.c_int32), ("chunks", ctypes.c_int64),
                 ("moved_chunks", ctypes.c_int64), ("old_bytes", ctypes.c_int64), ("new_bytes", ctypes.c_int64),
                 ("file_bytes", ctypes.c_int64), ("data_off", ctypes.c_int64)]
+
+
+class IndexInfo(ctypes.Structure):          # hdrf_index_info (32 B)
+    _fields_ = [("index_log2", ctypes.c_int32), ("reserved", ctypes.c_int32), ("slots", ctypes.c_int64),
+                ("entries", ctypes.c_int64), ("table_bytes", ctypes.c_int64)]
 
 
 class GxLayout(ctypes.Structure):
@@ -218,6 +224,8 @@ def load():
                                      ctypes.c_int64]),
         "hdrf_compact": (ctypes.c_int64, [_vp, ctypes.c_int32, _u32p, ctypes.c_int32, ctypes.POINTER(CompactRow), _u8p,
                                           ctypes.c_int64, _i64p]),
+        "hdrf_index_info_get": (ctypes.c_int, [_vp, ctypes.POINTER(IndexInfo)]),
+        "hdrf_index_resize": (ctypes.c_int, [_vp, ctypes.c_int32]),
         "hdrf_gx_read_locate": (ctypes.c_int64, [_vp, _u8p, ctypes.c_int64, _vp]),
         "hdrf_gx_flush_fn": (ctypes.c_int64, [_vp, _vp, ctypes.c_int64]),
         "hdrf_gx_alloc_scan": (ctypes.c_int32, [_vp, _vp, _vp, _u8p, _u8p]),
@@ -748,6 +756,20 @@ class Context:
                     if r["status"] == 0 and r["data_off"] >= 0:
                         files[r["id"]] = buf[r["data_off"]:r["data_off"] + r["file_bytes"]].tobytes()
             return out, files
+
+    def index_info(self):
+        """hdrf_index_info_get: dict(index_log2, slots, entries, table_bytes) of the fingerprint table as it
+        is now.  entries / slots is the load to watch: the write path is at full speed up to about 0.6."""
+        info = IndexInfo()
+        self._ck(self.L.hdrf_index_info_get(self._h, ctypes.byref(info)))
+        return {f: getattr(info, f) for f, _ in IndexInfo._fields_ if f != "reserved"}
+
+    def index_resize(self, new_log2):
+        """hdrf_index_resize: move the live entries into a table of 2^new_log2 slots, online and all or
+        nothing (HdrfError -4 when they would load it past 75 %; nothing changes then).  Every entry keeps
+        its 64 bytes; recipes, containers, the allocator and open receives are untouched."""
+        self._ck(self.L.hdrf_index_resize(self._h, new_log2))
+        self.cfg.index_log2 = new_log2
 
     def container(self, cid):
         closed = ctypes.c_int32(0)

@@ -75,6 +75,25 @@ class HipReductionScheme(ReductionScheme):
         (per-container rows, {container id: its new chunkDir file})."""
         return self.ctx.compact(ids, dry=dry, want_files=want_files)
 
+    def index_info(self):
+        """The fingerprint table now: dict(index_log2, slots, entries, table_bytes)."""
+        return self.ctx.index_info()
+
+    def resize_index(self, new_log2):
+        """Move the index into a table of 2^new_log2 slots while the scheme keeps running; a shrink that
+        would load the table past 75 % is refused (HdrfError -4) and changes nothing."""
+        self.ctx.index_resize(new_log2)
+
+    def grow_index_if_loaded(self, threshold=0.6):
+        """Grow the table by one bit when entries > threshold * slots (the write path slows past about
+        60 % load).  Returns the new log2, or None when the table was left alone.  Nothing calls this
+        implicitly: the DataNode decides when, e.g. after every few thousand blocks."""
+        info = self.index_info()
+        if info["entries"] <= threshold * info["slots"]:
+            return None
+        self.ctx.index_resize(info["index_log2"] + 1)
+        return info["index_log2"] + 1
+
     def recipe(self, block_id):
         return self.ctx.recipe(block_id)
 

@@ -237,7 +237,9 @@ int hdrf_batch_seg_trace(hdrf_ctx *ctx, int32_t b, hdrf_seg_trace *out, int64_t 
 int hdrf_index_get(hdrf_ctx *ctx, const uint8_t *digest, uint8_t out11[11]);
 int64_t hdrf_index_count(hdrf_ctx *ctx);
 /* Probe lengths of the last completed batch: each chunk's distance (entries) from its home slot to
- * the entry its digest resolved to (linear probing); sum, max and chunk count.  Measurement only. */
+ * the entry its digest resolved to (linear probing); sum, max and chunk count.  Measurement only.
+ * After hdrf_index_resize the batch's slots are those of the old table: all three are 0 until a batch
+ * has completed in the new one. */
 int hdrf_probe_stats(hdrf_ctx *ctx, int64_t *probe_sum, int64_t *probe_max, int64_t *chunks);
 /* All (digest, value) pairs sorted by digest; returns count (or HDRF_E_CAPACITY). */
 int64_t hdrf_index_dump(hdrf_ctx *ctx, uint8_t *keys, uint8_t *vals, int64_t cap);
@@ -498,6 +500,52 @@ typedef struct {
 } hdrf_compact_row;
 int64_t hdrf_compact(hdrf_ctx *ctx, int32_t flags, const uint32_t *ids, int32_t n, hdrf_compact_row *rows, uint8_t *out,
                      int64_t out_cap, int64_t *need);
+
+/* The size of the fingerprint table, online.  cfg.index_log2 is only the size the context opens with:
+ * hdrf_index_info_get tells how loaded the table is, hdrf_index_resize moves it into a table of another
+ * size while the context lives on.  The write path runs at full speed up to about 60 % load (DESIGN.md
+ * §7b), so a DataNode watches entries / slots and grows the table by one bit before that line; after
+ * deletes, hdrf_gc and hdrf_compact it may shrink the table again.
+ * hdrf_index_info_get is a view: it completes the batches in flight and applies a pending
+ * hdrf_reset_async, as hdrf_index_count does; `entries` is counted on the device.
+ * hdrf_index_resize:
+ *   When it runs   it takes the context lock, completes the batches in flight and applies a pending
+ *                  hdrf_reset_async, like the other views (a context an earlier failure marked lost
+ *                  answers as they do).  Single-node contexts (HDRF_E_UNSUPPORTED when n_ranks > 1).
+ *                  An open packet receive is allowed, unlike hdrf_gc and hdrf_reset: a receive buffer
+ *                  holds block bytes only, and hdrf_append_packet reads and writes neither the table
+ *                  nor its size, so receivers may keep appending while the call runs.
+ *   Arguments      new_log2 outside [10, 31]: HDRF_E_INVAL.  new_log2 equal to the current size: 0,
+ *                  nothing happens.  HDRF_E_CAPACITY when entries * 4 > 3 * 2^new_log2: a table more
+ *                  than 75 % full is one the write path cannot use (that line lies between the 60 % at
+ *                  which claim still runs at full speed and the 80 % at which it ran 3.4x slower), so
+ *                  a shrink never produces one; growing never trips it.  HDRF_E_NOMEM when the new
+ *                  table cannot be allocated: both tables are resident during the call.
+ *   Changes        afterwards the table has 2^new_log2 slots and holds exactly the live entries it
+ *                  held before, each one's 64 bytes unchanged (tag, batch, nCopy, container, start,
+ *                  stop, digest bytes, the batch-local fields as they stood): only the slot an entry
+ *                  sits in differs.  No new epoch; the batch counter, allocator, arena, recipes, loaded
+ *                  containers, drain bookkeeping, receive buffers and stats are untouched, so a later
+ *                  write deduplicates against the moved entries exactly as it would have against the
+ *                  old table, and hdrf_index_dump returns the same rows.  hdrf_probe_stats speaks of
+ *                  slots of the table the last batch ran in: after a resize it reports zeros
+ *                  (chunks = 0) until a batch has completed in the new table.
+ *   All or nothing the live entries are counted, the load rule checked, the new table allocated,
+ *                  cleared and filled, its live entries counted; only when the two counts agree and
+ *                  the fill reported no error does the context switch to the new table and free the
+ *                  old one.  Any failure before that (HDRF_E_NOMEM, HDRF_E_HIP, or HDRF_E_DEVICE when
+ *                  the counts disagree) frees the new table and leaves the context exactly as it was:
+ *                  the old table is only ever read, so there is no lost state.
+ * Nothing extra makes the new size durable: hdrf_index_dump does not depend on the capacity. */
+typedef struct {
+    int32_t index_log2;      /* the table's capacity now: 2^index_log2 slots */
+    int32_t reserved;        /* 0 */
+    int64_t slots;           /* 1 << index_log2 */
+    int64_t entries;         /* live entries (== hdrf_index_count) */
+    int64_t table_bytes;     /* slots * 64 */
+} hdrf_index_info;
+int hdrf_index_info_get(hdrf_ctx *ctx, hdrf_index_info *out);
+int hdrf_index_resize(hdrf_ctx *ctx, int32_t new_log2);
 
 /* Device memory helpers for callers without their own allocator (bench, tests). */
 int hdrf_dev_alloc(hdrf_ctx *ctx, uint64_t bytes, void **out);

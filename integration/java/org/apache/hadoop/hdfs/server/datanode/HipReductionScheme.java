@@ -218,6 +218,26 @@ public final class HipReductionScheme extends ReductionScheme {
     return done;
   }
 
+  /**
+   * The fingerprint table as it is now: {index_log2, slots, entries, table_bytes}.  The write path runs
+   * at full speed while entries / slots stays under about 0.6.
+   */
+  public long[] indexInfo() throws IOException {
+    long[] info = new long[4];
+    ByteBuffer.wrap(indexInfo0(ctx)).asLongBuffer().get(info);    // 8 bytes big-endian each
+    return info;
+  }
+
+  /**
+   * Move the index into a table of 2^newLog2 slots while the DataNode keeps running: grow by one bit
+   * when indexInfo() shows more than 60 % load, shrink after deletes, gc() and compact().  Receivers
+   * may stay open.  A shrink that would load the table past 75 % is refused and changes nothing; the
+   * new size needs no persisting of its own, the index dump does not depend on it.
+   */
+  public void resizeIndex(int newLog2) throws IOException {
+    resizeIndex0(ctx, newLog2);
+  }
+
   @Override
   public long length(long blockId) throws IOException {
     return length0(ctx, blockId);
@@ -242,6 +262,8 @@ public final class HipReductionScheme extends ReductionScheme {
   private static native void deleteBlock0(long ctx, long blockId) throws IOException;
   private static native byte[] gc0(long ctx) throws IOException;
   private static native byte[] compact0(long ctx, String chunkDir, long[] ids) throws IOException;
+  private static native byte[] indexInfo0(long ctx) throws IOException;
+  private static native void resizeIndex0(long ctx, int newLog2) throws IOException;
   private static native void reduce0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void submit0(long ctx, ByteBuffer direct, int len, long blockId) throws IOException;
   private static native void wait0(long ctx) throws IOException;

@@ -425,6 +425,35 @@ JNIEXPORT jbyteArray JNICALL JFN(compact0)(JNIEnv *env, jclass cls, jlong h, jst
     return r;
 }
 
+/* The fingerprint table now (hdrf_index_info_get): index_log2, slots, entries, table_bytes, 8 bytes
+ * big-endian each as gc0's ids are (HipReductionScheme.indexInfo() turns them into its long[]), so the
+ * DataNode can watch entries / slots and grow the table before 60 % load. */
+JNIEXPORT jbyteArray JNICALL JFN(indexInfo0)(JNIEnv *env, jclass cls, jlong h)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    hdrf_index_info info;
+    int rc = hdrf_index_info_get(ctx, &info);
+    if (rc) { throw_io(env, ctx, rc); return NULL; }
+    const int64_t v[4] = {info.index_log2, info.slots, info.entries, info.table_bytes};
+    uint8_t be[32];
+    for (int i = 0; i < 4; i++)
+        for (int b = 0; b < 8; b++) be[i * 8 + b] = (uint8_t)((uint64_t)v[i] >> (8 * (7 - b)));
+    jbyteArray out = (*env)->NewByteArray(env, 32);
+    if (out) (*env)->SetByteArrayRegion(env, out, 0, 32, (const jbyte *)be);
+    return out;
+}
+
+/* Move the index into a table of 2^newLog2 slots, online and all or nothing (hdrf_index_resize).  A
+ * refusal (HDRF_E_CAPACITY: the entries would load the new table past 75 %) changes nothing. */
+JNIEXPORT void JNICALL JFN(resizeIndex0)(JNIEnv *env, jclass cls, jlong h, jint newLog2)
+{
+    (void)cls;
+    hdrf_ctx *ctx = (hdrf_ctx *)(intptr_t)h;
+    int rc = hdrf_index_resize(ctx, (int32_t)newLog2);
+    if (rc) throw_io(env, ctx, rc);
+}
+
 /* stream mode (compressor 0 SnappyCodec / 3 LzopCodec / 4 Lz4Codec / 5 GzipCodec): the block's chunkDir
  * file for packet writes.  LzopCodec headers carry the wall clock, as LzopOutputStream writes
  * System.currentTimeMillis() / 1000. */
