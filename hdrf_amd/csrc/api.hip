@@ -96,6 +96,8 @@ static void free_all(hdrf_ctx *ctx)
     ctx->loaded.clear();
     for (auto p : ctx->rchunks) (void)hipFree(p);
     ctx->rchunks.clear();
+    for (auto p : ctx->schunks) (void)hipFree(p);
+    ctx->schunks.clear();
     void *ptrs[] = {ctx->d_tab, ctx->d_arena, ctx->d_alloc, ctx->d_stage, ctx->d_rd, ctx->d_gx_counts,
                     ctx->d_gx_rcounts, ctx->d_oslot, ctx->d_oflags, ctx->d_carena, ctx->d_fn, ctx->d_gx_x3exp,
                     ctx->d_x3want, ctx->d_gxst, ctx->d_gx_err};
@@ -251,6 +253,9 @@ void host::reset_host(hdrf_ctx *ctx)
     ctx->recipes.clear();
     ctx->rcur = 0;
     ctx->rhead = 0;
+    ctx->seeks.clear();                              // (the seek store's chunks are refilled from the start, as the recipes')
+    ctx->scur = 0;
+    ctx->shead = 0;
     ctx->lengths.clear();
     ctx->stats = hdrf_stats{};
 }
@@ -802,6 +807,7 @@ int host::recipe_alloc(hdrf_ctx *ctx, uint64_t bytes, uint32_t key, uint32_t n, 
     }
     *dst = ctx->rchunks[ctx->rcur] + ctx->rhead;
     ctx->recipes[key] = hdrf_ctx::RecipeLoc{ctx->rcur, ctx->rhead, n};
+    ctx->seeks.erase(key);                           // a seek table describes the recipe it was built from
     ctx->rhead += (bytes + 15) & ~15ull;
     return 0;
 }

@@ -26,6 +26,7 @@ extern "C" int hdrf_block_delete(hdrf_ctx *ctx, uint64_t block_id)
         ctx->recipes.erase(r);                           // its digests stay in the append-only recipe store
     }
     if (l != ctx->lengths.end()) ctx->lengths.erase(l);
+    ctx->seeks.erase(key);                               // its seek table goes with it
     return 0;
 }
 

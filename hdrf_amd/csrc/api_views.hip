@@ -8,6 +8,7 @@
 // (pend_closed, undrained, handed) and the drain job list (h_xfer).
 #include "ctx.hpp"
 #include "read_plan.hpp"
+#include "seek_plan.hpp"
 
 // ---- index views ------------------------------------------------------------------------
 // an entry's digest bytes (index_entry.hpp: the words are little-endian loads of them)
@@ -582,20 +583,33 @@ static uint32_t read_tile()
 
 // hdrf_read_batch with the arguments checked, the lock held and the batches in flight completed.
 // Everything is enqueued on ctx->st; the one host wait follows the status read-back.
-static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
+//
+// A request that names a stored recipe whose block has a seek table (hdrf_seek_build) is served from
+// the table: sk_span + sk_lookup (seek.hip) fill only the rows of the chunks under its range, sized by
+// seek_row_bound before the device knows the span.  The descriptors are uploaded with the table-less
+// requests first (`order`), so rv_lookup + rv_scan run over a prefix of them exactly as without tables,
+// the seek kernels over the rest, and one rv_gather over all.  bad_chunk != nullptr (n entries): the
+// verified read: vf_items + vf_hash re-hash every chunk under every successful range behind the gather.
+static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req, int64_t *bad_chunk = nullptr)
 {
+    const bool verify = bad_chunk != nullptr;
+    ctx->seek_last_rows = ctx->seek_last_reqs = 0;
     if (n == 0) return 0;
     const uint32_t T = read_tile();
     const int H = ctx->H;
     std::vector<ReadDesc> desc((size_t)n);
     std::vector<int64_t> pre((size_t)n, 0);              // what the host decides: < 0 fails the request
     std::vector<uint64_t> dig_off((size_t)n, 0);         // caller-supplied digests: offset in the scratch
+    std::vector<uint64_t> nrows((size_t)n, 0), nlen((size_t)n, 0);
+    std::vector<SeekReq> sreq((size_t)n, SeekReq{});     // end != 0: the request is served from a table
     uint64_t dig_bytes = 0;
-    ReadPrefix px;
+    int nseek = 0;
     for (int i = 0; i < n; i++) {
+        if (verify) bad_chunk[i] = -1;
         const hdrf_read_req &q = req[i];
         ReadDesc &d = desc[(size_t)i];
         d = ReadDesc{};
+        const hdrf_ctx::SeekLoc *tbl = nullptr;
         uint64_t size = 0, cnt = 0, clen = 0;
         if (q.recipe) {
             if (q.recipe_len < 4 || (q.recipe_len - 4) % H) pre[i] = HDRF_E_INVAL;
@@ -610,6 +624,8 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
                 size = (uint64_t)ctx->lengths[(uint32_t)q.block_id];
                 cnt = it->second.n;
                 d.dig = (uint64_t)(uintptr_t)(ctx->rchunks[it->second.chunk] + it->second.off);
+                auto sk = ctx->seeks.find((uint32_t)q.block_id);
+                if (sk != ctx->seeks.end() && sk->second.n == it->second.n) tbl = &sk->second;
             }
         }
         if (!pre[i] && !read_clip(size, q.offset, q.length, &clen)) pre[i] = HDRF_E_INVAL;
@@ -627,15 +643,45 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
                 dig_off[i] = dig_bytes;
                 dig_bytes += cnt * H;                    // H is a multiple of 4: the words stay aligned
             }
+            if (tbl) {                                   // the span's rows; sk_span writes how many it has
+                SeekReq &s = sreq[(size_t)i];
+                s.end = (uint64_t)(uintptr_t)(ctx->schunks[tbl->chunk] + tbl->off);
+                s.n = tbl->n;
+                cnt = seek_row_bound(tbl->n, clen, tbl->minlen);
+                s.cap = (uint32_t)cnt;
+                d.n = 0;
+                nseek++;
+            }
         }
-        if (!px.add((uint32_t)cnt, d.out, clen, T, &d.row0, &d.tile0))
+        nrows[(size_t)i] = cnt;
+        nlen[(size_t)i] = clen;
+    }
+    // the upload order: the requests without a table, then those with one, each kind in the caller's order
+    std::vector<int> order;
+    order.reserve((size_t)n);
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n; i++)
+            if ((sreq[(size_t)i].end != 0) == (pass == 1)) order.push_back(i);
+    const int nold = n - nseek;
+    ReadPrefix px;
+    uint64_t rows_old = 0;
+    for (int p = 0; p < n; p++) {
+        ReadDesc &d = desc[(size_t)order[(size_t)p]];
+        if (p == nold) rows_old = px.rows;
+        if (!px.add((uint32_t)nrows[(size_t)order[(size_t)p]], d.out, nlen[(size_t)order[(size_t)p]], T, &d.row0, &d.tile0))
             return set_err(ctx, HDRF_E_CAPACITY, "read batch: too many chunks or tiles for one call");
     }
+    if (nseek == 0) rows_old = px.rows;
+    ctx->seek_last_rows = (int64_t)px.rows;
+    ctx->seek_last_reqs = nseek;
     Readable rd;
     readable_list(ctx, rd);
     const uint32_t ncont = (uint32_t)rd.cid.size();
-    const ReadLayout L = read_layout((uint32_t)n, ncont, dig_bytes, px.rows, (uint32_t)sizeof(RdChunk));
-    if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, L.total)) return rc == HDRF_E_HIP ? HDRF_E_NOMEM : rc;
+    const bool extra = nseek || verify;                  // SeekReq rows and readable bounds behind the digests
+    const ReadLayout L = read_layout((uint32_t)n, ncont, extra ? seek_extra_upload(dig_bytes, (uint32_t)n, ncont) : dig_bytes,
+                                     px.rows, (uint32_t)sizeof(RdChunk));
+    const SeekLayout SL = seek_layout(L, dig_bytes, (uint32_t)n, px.rows, (uint32_t)sizeof(VfReadItem), verify);
+    if (int rc = grow(ctx, &ctx->d_rd, &ctx->rd_cap, SL.total)) return rc == HDRF_E_HIP ? HDRF_E_NOMEM : rc;
     uint8_t *R = ctx->d_rd;
     std::vector<uint8_t> up(L.upload, 0);
     for (int i = 0; i < n; i++) {
@@ -643,33 +689,94 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
         desc[i].dig = (uint64_t)(uintptr_t)(R + L.o_dig + dig_off[i]);
         std::memcpy(up.data() + L.o_dig + dig_off[i], req[i].recipe + 4, (size_t)desc[i].n * H);
     }
-    std::memcpy(up.data() + L.o_desc, desc.data(), desc.size() * sizeof(ReadDesc));
+    for (int p = 0; p < n; p++) {
+        std::memcpy(up.data() + L.o_desc + (size_t)p * sizeof(ReadDesc), &desc[(size_t)order[(size_t)p]], sizeof(ReadDesc));
+        if (extra) std::memcpy(up.data() + SL.o_sreq + (size_t)p * sizeof(SeekReq), &sreq[(size_t)order[(size_t)p]], sizeof(SeekReq));
+    }
     if (ncont) {
         std::memcpy(up.data() + L.o_cid, rd.cid.data(), (size_t)ncont * 4);
         std::memcpy(up.data() + L.o_base, rd.base.data(), (size_t)ncont * 8);
+        if (extra) std::memcpy(up.data() + SL.o_alloc, rd.alloc.data(), (size_t)ncont * 8);
     }
     hipStream_t st = ctx->st;
-    std::vector<int> status((size_t)n, 0);
+    std::vector<int> status((size_t)n, 0);               // in upload order, as everything read back below
+    std::vector<uint32_t> vbad((size_t)n, 0xffffffffu);
+    VfCounters vc{};
+    ReadDesc *d_desc = (ReadDesc *)(R + L.o_desc);
+    SeekReq *d_sreq = (SeekReq *)(R + SL.o_sreq);
+    const uint32_t *d_cid = (const uint32_t *)(R + L.o_cid);
+    const uint64_t *d_base = (const uint64_t *)(R + L.o_base);
+    RdChunk *d_rows = (RdChunk *)(R + L.o_rows);
+    int *d_status = (int *)(R + L.o_status);
     HIPCK(hipMemcpyAsync(R, up.data(), up.size(), hipMemcpyHostToDevice, st));
-    HIPCK(hipMemsetAsync(R + L.o_status, 0, (size_t)n * 4, st));
-    HIPCK(launch_readv(ctx->cfg.hasher, (const ReadDesc *)(R + L.o_desc), n, (uint32_t)px.rows, (uint32_t)px.tiles, T,
-                       ctx->d_tab, ctx->cfg.index_log2, tag_mask(ctx), (const uint32_t *)(R + L.o_cid),
-                       (const uint64_t *)(R + L.o_base), (int)ncont, (RdChunk *)(R + L.o_rows), (int *)(R + L.o_status), st));
-    HIPCK(hipMemcpyAsync(status.data(), R + L.o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemsetAsync(d_status, 0, (size_t)n * 4, st));
+    if (nseek == 0) {
+        HIPCK(launch_readv(ctx->cfg.hasher, d_desc, n, (uint32_t)px.rows, (uint32_t)px.tiles, T, ctx->d_tab, ctx->cfg.index_log2,
+                           tag_mask(ctx), d_cid, d_base, (int)ncont, d_rows, d_status, st));
+    } else {
+        // lookup + scan over the table-less prefix, span + lookup over the rest, then one gather over all
+        HIPCK(launch_readv(ctx->cfg.hasher, d_desc, nold, (uint32_t)rows_old, 0, T, ctx->d_tab, ctx->cfg.index_log2,
+                           tag_mask(ctx), d_cid, d_base, (int)ncont, d_rows, d_status, st));
+        HIPCK(launch_seek_lookup(ctx->cfg.hasher, d_desc + nold, d_sreq + nold, nseek, (uint32_t)rows_old,
+                                 (uint32_t)(px.rows - rows_old), ctx->d_tab, ctx->cfg.index_log2, tag_mask(ctx), d_cid,
+                                 (int)ncont, d_rows, d_status + nold, st));
+        HIPCK(launch_readv(ctx->cfg.hasher, d_desc, n, 0, (uint32_t)px.tiles, T, ctx->d_tab, ctx->cfg.index_log2,
+                           tag_mask(ctx), d_cid, d_base, (int)ncont, d_rows, d_status, st));
+    }
+    if (verify) {
+        HIPCK(hipMemsetAsync(R + SL.o_bad, 0xff, (size_t)n * 4, st));
+        HIPCK(hipMemsetAsync(R + SL.o_cnt, 0, sizeof vc, st));
+        HIPCK(launch_vf_read_items(ctx->cfg.hasher, d_desc, d_sreq, n, (uint32_t)px.rows, d_rows, d_status, d_base,
+                                   (const uint64_t *)(R + SL.o_alloc), (VfReadItem *)(R + SL.o_items),
+                                   (uint32_t *)(R + SL.o_bad), (VfCounters *)(R + SL.o_cnt), st));
+        if (px.rows)
+            HIPCK(launch_vf_hash_range(ctx->cfg.hasher, (const VfReadItem *)(R + SL.o_items), (uint32_t *)(R + SL.o_bad),
+                                       (VfCounters *)(R + SL.o_cnt), vf_workgroups(ctx), st));
+        HIPCK(hipMemcpyAsync(vbad.data(), R + SL.o_bad, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(&vc, R + SL.o_cnt, sizeof vc, hipMemcpyDeviceToHost, st));
+    }
+    HIPCK(hipMemcpyAsync(status.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
+    if (verify && vc.checked != vc.n_items) return set_err(ctx, HDRF_E_DEVICE, "verified read: not every chunk was hashed");
+    std::vector<int> place((size_t)n, 0);                // request -> its place in the upload order
+    for (int p = 0; p < n; p++) place[(size_t)order[(size_t)p]] = p;
     int first = 0;
     for (int i = 0; i < n; i++) {
+        const int p = place[(size_t)i];
+        const bool seek = sreq[(size_t)i].end != 0;
         int64_t r = pre[i];
-        const char *why = r == HDRF_E_NOTFOUND ? "no recipe for this block (keep_recipes?)"
+        std::string why = r == HDRF_E_NOTFOUND ? "no recipe for this block (keep_recipes?)"
                           : r == HDRF_E_DEVICE ? "recipe without digests" : "bad recipe, offset past the block's end or no output";
-        if (!r && (status[i] & kReadNotFound)) {
+        if (!r && (status[p] & kReadNotFound)) {
             r = HDRF_E_NOTFOUND;
             why = "a recipe digest is not in the index, or a container of the range is not readable";
-        } else if (!r && (status[i] & kReadDevice)) {
+        } else if (!r && (status[p] & kReadDevice)) {
             r = HDRF_E_DEVICE;
-            why = "chunk lengths do not add up to the recipe size";
+            why = seek ? "the block's seek table and the index disagree on a chunk's length (hdrf_seek_build again)"
+                       : "chunk lengths do not add up to the recipe size";
+        } else if (!r && verify && vbad[(size_t)p] != 0xffffffffu) {
+            r = HDRF_E_CORRUPT;
+            bad_chunk[i] = vbad[(size_t)p];
+            if (!first) {                                // name the chunk: its digest, and the row the lookup made for it
+                const uint32_t k = vbad[(size_t)p];
+                std::vector<uint8_t> dg((size_t)H, 0);
+                if (req[i].recipe) std::memcpy(dg.data(), req[i].recipe + 4 + (size_t)k * H, (size_t)H);
+                else {
+                    const hdrf_ctx::RecipeLoc &rl = ctx->recipes[(uint32_t)req[i].block_id];
+                    HIPCK(hipMemcpy(dg.data(), ctx->rchunks[rl.chunk] + rl.off + (size_t)k * H, (size_t)H, hipMemcpyDeviceToHost));
+                }
+                SeekReq sq{};
+                if (seek) HIPCK(hipMemcpy(&sq, d_sreq + p, sizeof sq, hipMemcpyDeviceToHost));
+                RdChunk c{};
+                HIPCK(hipMemcpy(&c, d_rows + desc[(size_t)i].row0 + (k - sq.k0), sizeof c, hipMemcpyDeviceToHost));
+                const std::string where = c.slot < rd.cid.size() ? "container " + std::to_string(rd.cid[c.slot]) : std::string("no container");
+                why = "recipe position " + std::to_string(k) + ": digest " + hex_digest(dg.data(), H) + ", " + where + " [" +
+                      std::to_string(c.start) + ", " + std::to_string((uint64_t)c.start + c.len) +
+                      "): the bytes hash to another digest (" + std::to_string(vc.n_bad) + " of " + std::to_string(vc.n_items) +
+                      " chunks under the call's ranges)";
+            }
         }
-        req[i].result = r ? r : (int64_t)desc[i].len;
+        req[i].result = r ? r : (int64_t)desc[i].len;     // (HDRF_E_CORRUPT: the bytes are in the output anyway)
         if (r && !first) first = set_err(ctx, (int)r, "read request " + std::to_string(i) + ": " + why);
     }
     return first;
@@ -677,21 +784,34 @@ static int read_batch_body(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
 
 static_assert(sizeof(hdrf_read_req) == 56, "hdrf_read_req: ctypes mirror ReadReq in hdrf_amd/lib.py");
 
+// hdrf_read_batch (bad_chunk == nullptr) and hdrf_read_batch_verified
+static int read_batch_entry(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req, int64_t *bad_chunk)
+{
+    if (n < 0 || n > HDRF_READ_MAX_REQS) return set_err(ctx, HDRF_E_INVAL, "read batch: n outside [0, HDRF_READ_MAX_REQS]");
+    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "ranged reads on node-global contexts");
+    if (int rc = drain(ctx)) return rc;
+    return read_batch_body(ctx, n, req, bad_chunk);
+}
+
 extern "C" int hdrf_read_batch(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req)
 {
     HDRF_LOCK(ctx);
     if (!ctx || !req) return HDRF_E_INVAL;
-    if (n < 0 || n > HDRF_READ_MAX_REQS) return set_err(ctx, HDRF_E_INVAL, "read batch: n outside [0, HDRF_READ_MAX_REQS]");
-    if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "ranged reads on node-global contexts");
-    if (int rc = drain(ctx)) return rc;
-    return read_batch_body(ctx, n, req);
+    return read_batch_entry(ctx, n, req, nullptr);
 }
 
-extern "C" int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out,
-                                   int64_t cap)
+extern "C" int hdrf_read_batch_verified(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req, int64_t *bad_chunk)
 {
     HDRF_LOCK(ctx);
-    if (!ctx) return HDRF_E_INVAL;
+    if (!ctx || !req || !bad_chunk) return HDRF_E_INVAL;
+    return read_batch_entry(ctx, n, req, bad_chunk);
+}
+
+// hdrf_read_range (bad_chunk == nullptr) and hdrf_read_range_verified
+static int64_t read_range_body(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out, int64_t cap,
+                               int64_t *bad_chunk)
+{
+    if (bad_chunk) *bad_chunk = -1;
     if (ctx->G > 1) return set_err(ctx, HDRF_E_UNSUPPORTED, "ranged reads on node-global contexts");
     if (int rc = drain(ctx)) return rc;                  // blocks in flight first: their recipes are SET
     uint64_t clen = 0;
@@ -707,8 +827,29 @@ extern "C" int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t of
     q.offset = offset;
     q.length = length;
     q.dev_out = ctx->d_stage;
-    const int rc = read_batch_body(ctx, 1, &q);
+    const int rc = read_batch_body(ctx, 1, &q, bad_chunk);
+    if (rc == HDRF_E_CORRUPT && q.result == HDRF_E_CORRUPT) {        // the range's bytes are in the output anyway
+        const std::string why = ctx->err;
+        if (clen) HIPCK(hipMemcpy(out, ctx->d_stage, (size_t)clen, hipMemcpyDeviceToHost));
+        return set_err(ctx, HDRF_E_CORRUPT, "block " + std::to_string(block_id) + ", " + why);
+    }
     if (rc) return rc;
     if (q.result > 0) HIPCK(hipMemcpy(out, ctx->d_stage, (size_t)q.result, hipMemcpyDeviceToHost));
     return q.result;
+}
+
+extern "C" int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out,
+                                   int64_t cap)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx) return HDRF_E_INVAL;
+    return read_range_body(ctx, block_id, offset, length, out, cap, nullptr);
+}
+
+extern "C" int64_t hdrf_read_range_verified(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out,
+                                            int64_t cap, int64_t *bad_chunk)
+{
+    HDRF_LOCK(ctx);
+    if (!ctx || !bad_chunk) return HDRF_E_INVAL;
+    return read_range_body(ctx, block_id, offset, length, out, cap, bad_chunk);
 }

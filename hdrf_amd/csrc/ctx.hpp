@@ -1,10 +1,11 @@
 // ctx.hpp — the context behind the C-ABI (include/hdrf.h) and the host functions its translation
 // units share.  Internal: included only by the api*.hip files (api.hip core and batch pipeline,
 // api_rx.hip packet receive, api_stream.hip stream codecs, api_gx.hip node-global phases,
-// api_views.hip views / restore / drain / reconstruction, api_verify.hip scrub, api_gc.hip block deletion and
-// index garbage collection, api_compact.hip container compaction, api_resize.hip online table resize); each of them names in its header comment
-// the context state it may write.  Everything here but hdrf_ctx itself lives in hdrf::host, hidden
-// from the library's dynamic symbols.
+// api_views.hip views / restore / drain / reconstruction, api_seek.hip seek tables,
+// api_verify.hip scrub, api_gc.hip block deletion and index garbage collection, api_compact.hip
+// container compaction, api_resize.hip online table resize); each of them names in its header
+// comment the context state it may write.  Everything here but hdrf_ctx itself lives in
+// hdrf::host, hidden from the library's dynamic symbols.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -194,6 +195,15 @@ struct hdrf_ctx {
     uint64_t rhead = 0;                               // bytes used in it
     std::map<uint32_t, RecipeLoc> recipes;
     std::map<uint32_t, int64_t> lengths;              // block length (recipe head)
+    // seek tables (hdrf_seek_build, api_seek.hip): end[] of a stored recipe, u32 per chunk, in an
+    // append-only device store of its own (the recipe store stays digests end to end: hdrf_gc walks
+    // it); the host keeps where each table is.  minlen: the smallest length among chunks 0..n-2.
+    struct SeekLoc { uint32_t chunk; uint64_t off; uint32_t n; uint32_t minlen; };
+    std::vector<uint8_t *> schunks;
+    uint32_t scur = 0;                                // chunk being filled
+    uint64_t shead = 0;                               // bytes used in it
+    std::map<uint32_t, SeekLoc> seeks;
+    int64_t seek_last_rows = 0, seek_last_reqs = 0;   // the last read call (hdrf_seek_info)
     struct Loaded { uint8_t *ptr; uint64_t len; };
     std::map<uint32_t, Loaded> loaded;               // containers loaded back from files (read side)
     // node-global index (gx.hip): scratch aggregation table, owner-side per-record arrays

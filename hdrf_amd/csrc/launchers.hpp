@@ -288,6 +288,36 @@ hipError_t launch_vf_hash_block(int hasher, const RdChunk *chunks, int n, const 
                                 uint64_t block_bytes, VfCounters *C, int wgs, hipStream_t st);
 hipError_t launch_vf_rows(int hasher, const uint32_t *bad, uint32_t from, uint32_t n, const IndexEntry *tab,
                           uint64_t slot0, VfBadRow *out, hipStream_t st);
+// One chunk of a verified ranged read (seek.hip vf_items -> verify.hip vf_hash): the item carries its own
+// source (the request's output, or the chunk's container), how far that source may be read, where the
+// expected digest is, and whose chunk it is.
+struct VfReadItem {
+    uint64_t base;           // 4-B aligned device address at or below the chunk's first byte
+    uint64_t readable;       // bytes readable from base (to the output's end / the container's allocation)
+    uint64_t dig;            // device address of the recipe digest
+    uint32_t s0, len;        // the chunk is base[s0 .. s0 + len), s0 < 4
+    uint32_t req, pos;       // the request, and the chunk's position in its recipe
+};
+static_assert(sizeof(VfReadItem) == 40, "VfReadItem is read as five 8-B words");
+// hash the items (C->n_items, read on the device) against their recipe digests; bad[item.req] (0xffffffff
+// from the caller) takes the lowest failing recipe position of each request
+hipError_t launch_vf_hash_range(int hasher, const VfReadItem *items, uint32_t *bad, VfCounters *C, int wgs, hipStream_t st);
+// seek tables and verified ranged reads (seek.hip; the arithmetic is seek_plan.hpp's).
+struct SeekReq;
+// hdrf_seek_build: the rows launch_readv made for nreq zero-length requests -> end[] at dst[r] and
+// minlen[r] (0xffffffff from the caller), for the requests whose status is 0
+hipError_t launch_seek_store(const ReadDesc *req, int nreq, const RdChunk *rows, const int *status, const uint64_t *dst,
+                             uint32_t *minlen, hipStream_t st);
+// the span and the lookup of the nreq requests with a table, whose rows are [row_base, row_base + nrows);
+// writes req[r].n, req[r].dig and sq[r].k0, then the rows; status as launch_readv's
+hipError_t launch_seek_lookup(int hasher, ReadDesc *req, SeekReq *sq, int nreq, uint32_t row_base, uint32_t nrows,
+                              const IndexEntry *tab, int log2cap, unsigned long long key, const uint32_t *cids, int ncont,
+                              RdChunk *rows, int *status, hipStream_t st);
+// after the gather: the chunks under every successful request's range -> items (nrows of them at most),
+// C->n_items; an entry that reaches past its container's allocation is bad without being hashed
+hipError_t launch_vf_read_items(int hasher, const ReadDesc *req, const SeekReq *sq, int nreq, uint32_t nrows,
+                                const RdChunk *rows, const int *status, const uint64_t *bases, const uint64_t *allocs,
+                                VfReadItem *items, uint32_t *bad, VfCounters *C, hipStream_t st);
 // index garbage collection (gc.hip; the flat-range arithmetic is gc_plan.hpp's).  Counters of one
 // collection, zeroed by the caller before the launches.
 struct GcJob;

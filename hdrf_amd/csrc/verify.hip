@@ -15,7 +15,9 @@
 //                cursor, so a 1,000,000-B forced-cut chunk never leaves 63 lanes idle.  Scrub: items from
 //                vf_collect, expected digest from the table entry (index_entry.hpp
 //                entry_digest_words).  Verified read: the items are the RdChunk rows (rd_chunk.hpp) of
-//                the lookup over the rebuilt block, expected digest from the recipe.
+//                the lookup over the rebuilt block, expected digest from the recipe.  Verified ranged
+//                read: the items are the VfReadItem rows of vf_items (seek.hip), each with a source of
+//                its own.
 //   vf_rows    — bad-list rows (table slot, reason) -> hdrf_bad_chunk records
 #include <algorithm>
 
@@ -104,12 +106,17 @@ __global__ void __launch_bounds__(256) vf_collect_kernel(const IndexEntry *__res
     }
 }
 
-// READ = false (scrub): items[0 .. *C.n_items) from vf_collect over slots slot0 + item.slot of tab;
+// MODE kVfScrub: items[0 .. *C.n_items) from vf_collect over slots slot0 + item.slot of tab;
 // base / readable of an item = bases / allocs[item.ridx].
-// READ = true (verified read): item k = chunk k of the rebuilt block: chunks[k].len bytes at
+// MODE kVfBlock (verified read): item k = chunk k of the rebuilt block: chunks[k].len bytes at
 // block_base + block_mis + chunks[k].off (block_base 4-B aligned, block_readable bytes readable from
 // it), expected digest dig[k * HW ..]; the lowest failing k lands in C.first_bad_inv (as ~k).
-template <int HW, bool READ>
+// MODE kVfRange (verified ranged read): `items` holds *C.n_items VfReadItem rows from vf_items (seek.hip),
+// each with its own source, readable bound and expected-digest address; the lowest failing recipe
+// position of request r lands in bad[r].  The pool hands out item numbers, and a lane loads its item
+// when it takes it.
+constexpr int kVfScrub = 0, kVfBlock = 1, kVfRange = 2;
+template <int HW, int MODE>
 __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__ items, const RdChunk *__restrict__ chunks,
                                                       uint32_t n_read, const uint32_t *__restrict__ dig,
                                                       const IndexEntry *__restrict__ tab, uint64_t slot0,
@@ -118,7 +125,9 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
                                                       uint32_t block_mis, uint64_t block_readable,
                                                       uint32_t *__restrict__ bad, VfCounters *__restrict__ C)
 {
-    const uint32_t n = READ ? n_read : C->n_items;            // (written by vf_collect, earlier on the stream)
+    constexpr bool READ = MODE == kVfBlock;
+    const VfReadItem *ritems = (const VfReadItem *)items;     // (kVfRange)
+    const uint32_t n = READ ? n_read : C->n_items;            // (written by vf_collect / vf_items, earlier on the stream)
     bool active = false, exhausted = false;
     uint32_t k = 0, s0 = 0, len = 0, T = 0, nb = 0, bi = 0;
     const uint8_t *base = block_base;
@@ -135,7 +144,11 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
         bool mism = false;
         if (done) {
             uint32_t want[HW];
-            if (READ) {
+            if (MODE == kVfRange) {
+                const uint32_t *d = (const uint32_t *)(uintptr_t)ritems[k].dig;
+#pragma unroll
+                for (int i = 0; i < HW; i++) want[i] = d[i];
+            } else if (READ) {
 #pragma unroll
                 for (int i = 0; i < HW; i++) want[i] = dig[(size_t)k * HW + i];
             } else {
@@ -151,7 +164,8 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
         if (ballot64(mism)) {
             const uint32_t bi_ = wave_append(&C->n_bad, mism);
             if (mism) {
-                if (READ) atomicMax(&C->first_bad_inv, ~k);    // the lowest failing position
+                if (MODE == kVfRange) atomicMin(bad + ritems[k].req, ritems[k].pos);
+                else if (READ) atomicMax(&C->first_bad_inv, ~k);    // the lowest failing position
                 else { bad[2 * (size_t)bi_] = k; bad[2 * (size_t)bi_ + 1] = 1u; }
             }
         }
@@ -171,7 +185,9 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
                 exhausted = (uint64_t)kbP + 64u >= n;          // wave-uniform
                 head = 0;
                 if (l < cntP) {
-                    if (READ) {
+                    if (MODE == kVfRange) {
+                        p0 = kbP + (uint32_t)l; p1 = 0u; p2 = 0u; p3 = 0u;
+                    } else if (READ) {
                         const RdChunk c = chunks[kbP + l];
                         p0 = kbP + (uint32_t)l; p1 = 0u; p2 = c.off + block_mis; p3 = c.len;
                     } else {
@@ -188,7 +204,13 @@ __global__ void __launch_bounds__(256) vf_hash_kernel(const VfItem *__restrict__
                 k = q0;
                 s0 = q2;
                 len = q3;
-                if (!READ) {
+                if (MODE == kVfRange) {
+                    const VfReadItem it = ritems[q0];
+                    base = (const uint8_t *)(uintptr_t)it.base;
+                    readable = it.readable;
+                    s0 = it.s0;
+                    len = it.len;
+                } else if (!READ) {
                     base = (const uint8_t *)(uintptr_t)bases[q1];
                     readable = allocs[q1];
                 }
@@ -249,7 +271,7 @@ hipError_t launch_vf_hash_items(int hasher, const void *items, const IndexEntry 
 {
     const dim3 g(std::max(1, wgs));
     with_digest_words(hasher, [&](auto hw) {
-        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, false>), g, dim3(256), 0, st, (const VfItem *)items, nullptr,
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, kVfScrub>), g, dim3(256), 0, st, (const VfItem *)items, nullptr,
                            0u, nullptr, tab, slot0, bases, allocs, nullptr, 0u, 0ull, bad, C);
     });
     return hipGetLastError();
@@ -263,8 +285,18 @@ hipError_t launch_vf_hash_block(int hasher, const RdChunk *chunks, int n, const 
     const uint32_t mis = (uint32_t)((uintptr_t)block & 3u);
     const dim3 g(std::max(1, std::min(wgs, (n + 255) / 256)));
     with_digest_words(hasher, [&](auto hw) {
-        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, true>), g, dim3(256), 0, st, nullptr, chunks,
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, kVfBlock>), g, dim3(256), 0, st, nullptr, chunks,
                            (uint32_t)n, dig, nullptr, 0ull, nullptr, nullptr, block - mis, mis, block_bytes + mis, nullptr, C);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_vf_hash_range(int hasher, const VfReadItem *items, uint32_t *bad, VfCounters *C, int wgs, hipStream_t st)
+{
+    const dim3 g(std::max(1, wgs));
+    with_digest_words(hasher, [&](auto hw) {
+        hipLaunchKernelGGL((vf_hash_kernel<decltype(hw)::value, kVfRange>), g, dim3(256), 0, st, (const VfItem *)items, nullptr,
+                           0u, nullptr, nullptr, 0ull, nullptr, nullptr, nullptr, 0u, 0ull, bad, C);
     });
     return hipGetLastError();
 }

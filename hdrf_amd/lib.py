@@ -38,6 +38,7 @@ EXPORTS = [
     "hdrf_gx_place_wait", "hdrf_gx_sync", "hdrf_reset_async",
     "hdrf_scrub", "hdrf_reconstruct_verified", "hdrf_reconstruct_block_verified",
     "hdrf_read_batch", "hdrf_read_range",
+    "hdrf_seek_build", "hdrf_seek_drop", "hdrf_seek_info_get", "hdrf_read_batch_verified", "hdrf_read_range_verified",
     "hdrf_block_delete", "hdrf_gc",
     "hdrf_compact",
     "hdrf_index_info_get", "hdrf_index_resize",
@@ -107,6 +108,10 @@ class ReadReq(ctypes.Structure):            # hdrf_read_req (56 B)
     _fields_ = [("block_id", ctypes.c_uint64), ("recipe", ctypes.c_void_p), ("recipe_len", ctypes.c_int64),
                 ("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dev_out", ctypes.c_void_p),
                 ("result", ctypes.c_int64)]
+
+
+class SeekInfo(ctypes.Structure):           # hdrf_seek_info (40 B)
+    _fields_ = [(n, ctypes.c_int64) for n in ("blocks", "chunks", "bytes", "last_rows", "last_seek_reqs")]
 
 
 class GcStats(ctypes.Structure):            # hdrf_gc_stats (80 B)
@@ -219,6 +224,12 @@ def load():
         "hdrf_read_batch": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(ReadReq)]),
         "hdrf_read_range": (ctypes.c_int64, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u8p,
                                              ctypes.c_int64]),
+        "hdrf_seek_build": (ctypes.c_int, [_vp, _u64p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "hdrf_seek_drop": (ctypes.c_int, [_vp, _u64p, ctypes.c_int32]),
+        "hdrf_seek_info_get": (ctypes.c_int, [_vp, ctypes.POINTER(SeekInfo)]),
+        "hdrf_read_batch_verified": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(ReadReq), _i64p]),
+        "hdrf_read_range_verified": (ctypes.c_int64, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u8p,
+                                                      ctypes.c_int64, _i64p]),
         "hdrf_block_delete": (ctypes.c_int, [_vp, ctypes.c_uint64]),
         "hdrf_gc": (ctypes.c_int64, [_vp, ctypes.c_int32, ctypes.POINTER(GcStats), ctypes.POINTER(GcContainer),
                                      ctypes.c_int64]),
@@ -645,13 +656,16 @@ class Context:
                                                                       ctypes.byref(bad)), bad)
         return self._ck(self.L.hdrf_reconstruct(self._h, _p(r), r.size, dev_out, cap))
 
-    def read_batch(self, reqs):
+    def read_batch(self, reqs, verify=False):
         """hdrf_read_batch: up to READ_MAX_REQS byte ranges served by one set of launches.  reqs:
         (block, offset, length, dev_out) tuples, block = a block id (the stored recipe) or a recipe's
         bytes; dev_out = a device address (any alignment).  Returns the list of per-request results
         (bytes written, or a negative HDRF_E_* code: one failing request does not stop the others).
         Raises HdrfError only on a call-level failure; read_batch_code is the call's return value
-        (0, or the code of the lowest-numbered failing request)."""
+        (0, or the code of the lowest-numbered failing request).
+        verify=True (hdrf_read_batch_verified): every chunk under a successful range is re-hashed and
+        compared with its recipe digest; a request with a mismatch gets -8 (HDRF_E_CORRUPT), its bytes are
+        in its output anyway, and read_batch_bad[i] is its lowest failing recipe position (-1 otherwise)."""
         n = len(reqs)
         arr = (ReadReq * max(n, 1))()
         keep = []
@@ -663,21 +677,69 @@ class Context:
             else:
                 q.block_id = int(blk)
             q.offset, q.length, q.dev_out, q.result = int(off), int(length), dev, 0
-        rc = self.L.hdrf_read_batch(self._h, n, arr)
+        if verify:
+            bad = (ctypes.c_int64 * max(n, 1))()
+            rc = self.L.hdrf_read_batch_verified(self._h, n, arr, bad)
+            self.read_batch_bad = list(bad[:n])
+        else:
+            rc = self.L.hdrf_read_batch(self._h, n, arr)
         self.read_batch_code = rc
         results = [q.result for q in arr[:n]]
         if rc < 0 and not any(r == rc for r in results):
             self._ck(rc)
         return results
 
-    def read_range(self, block_id, offset, length):
+    def read_range(self, block_id, offset, length, verify=False):
         """hdrf_read_range: bytes [offset, offset + length) of a stored block, clipped to its end, as
-        np.uint8 (BlockSender's startOffset / length; only those bytes are gathered and copied)."""
+        np.uint8 (BlockSender's startOffset / length; only those bytes are gathered and copied).
+        verify=True (hdrf_read_range_verified): a chunk under the range that does not hash to its recipe
+        digest raises HdrfError (code -8, .bad_chunk = the lowest failing recipe position, .data = the
+        range's bytes as they were served)."""
         # (the block may belong to a batch still in flight, whose length only the call itself learns)
         cap = max(0, min(int(length), int(self.cfg.max_block_bytes)))
         out = np.empty(max(cap, 1), np.uint8)
+        if verify:
+            bad = ctypes.c_int64(-1)
+            try:
+                m = self._ck_verified(self.L.hdrf_read_range_verified(self._h, block_id, offset, length, _p(out), cap,
+                                                                      ctypes.byref(bad)), bad)
+            except HdrfError as e:
+                if e.code == -8:
+                    left = max(0, self.block_length(block_id) - int(offset))
+                    e.data = out[:min(cap, left)].copy()
+                raise
+            return out[:m].copy()
         m = self._ck(self.L.hdrf_read_range(self._h, block_id, offset, length, _p(out), cap))
         return out[:m].copy()
+
+    def seek_build(self, ids):
+        """hdrf_seek_build: build (or rebuild) the seek tables of the stored blocks `ids`, with which
+        read_batch / read_range look up only the chunks under a range.  Returns the per-id results (0, or
+        a negative HDRF_E_* code: one failing id does not stop the others); seek_build_code is the
+        call's return value.  Raises HdrfError only on a call-level failure."""
+        a = np.ascontiguousarray(ids, np.uint64)
+        n = int(a.size)
+        res = (ctypes.c_int32 * max(n, 1))()
+        rc = self.L.hdrf_seek_build(self._h, _p(a if n else np.zeros(1, np.uint64), _u64p), n, res)
+        self.seek_build_code = rc
+        out = list(res[:n])
+        if rc < 0 and not any(r == rc for r in out):
+            self._ck(rc)
+        return out
+
+    def seek_drop(self, ids=None):
+        """hdrf_seek_drop: forget the seek tables of `ids`; None: all of them, and free the store."""
+        if ids is None:
+            self._ck(self.L.hdrf_seek_drop(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(ids, np.uint64)
+        self._ck(self.L.hdrf_seek_drop(self._h, _p(a if a.size else np.zeros(1, np.uint64), _u64p), int(a.size)))
+
+    def seek_info(self):
+        """hdrf_seek_info_get: dict(blocks, chunks, bytes, last_rows, last_seek_reqs)."""
+        s = SeekInfo()
+        self._ck(self.L.hdrf_seek_info_get(self._h, ctypes.byref(s)))
+        return {f: getattr(s, f) for f, _ in SeekInfo._fields_}
 
     def scrub(self, container=None):
         """hdrf_scrub: every index entry whose container is readable re-hashed from the container's

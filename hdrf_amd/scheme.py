@@ -55,6 +55,12 @@ class HipReductionScheme(ReductionScheme):
 
     read_range = read
 
+    def prepare_reads(self, ids):
+        """Build the seek tables of the stored blocks `ids`, so that ranged reads of them look up only the
+        chunks under a range instead of the whole recipe.  Returns the per-id results (0 or an HDRF_E_*
+        code).  A table lasts until its block is deleted, rewritten or the context is reset."""
+        return self.ctx.seek_build(ids)
+
     def scrub(self, container=None):
         """Re-hash every stored chunk whose container is readable: (stats, bad chunks)."""
         return self.ctx.scrub(container)

@@ -375,6 +375,71 @@ typedef struct {
 int hdrf_read_batch(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req);
 int64_t hdrf_read_range(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out, int64_t cap);
 
+/* Seek tables.  Without one, a ranged read looks up EVERY digest of the block's recipe: a chunk's offset
+ * in the block is the sum of all earlier chunk lengths, and those live only in the index entries.  The
+ * seek table of a stored recipe of n chunks is end[0..n), u32: end[k] is the block offset one past chunk
+ * k.  The tables live in a device store of their own, beside the recipe store.
+ * hdrf_seek_build builds (or rebuilds) the tables of n >= 0 blocks:
+ *   When it runs   a view: it takes the context lock and completes the batches in flight, as
+ *                  hdrf_read_batch does.  Single-node contexts (HDRF_E_UNSUPPORTED when n_ranks > 1).
+ *   What it does   for every id it looks up every digest of the stored recipe, adds up the lengths and
+ *                  checks the total against the recipe size.  Only the index is needed: no container has
+ *                  to be readable.  The ids are worked through in groups, so the scratch stays bounded
+ *                  whatever n is.
+ *   Failures       per id, in result[i] (result may be NULL): HDRF_E_NOTFOUND when there is no stored
+ *                  recipe (which includes cfg.keep_recipes == 0) or a digest is absent from the index,
+ *                  HDRF_E_DEVICE when the lengths do not add up to the size.  A failed id keeps no table
+ *                  (an older table of it is dropped).  One failure does not stop the others; the call
+ *                  returns the code of the lowest-numbered failing id, 0 when there is none.  Call-level
+ *                  failures: HDRF_E_INVAL (NULL context, n < 0, n > 0 without ids), HDRF_E_NOMEM,
+ *                  HDRF_E_CAPACITY (a recipe of more than 2^24 chunks), HDRF_E_HIP.
+ *   Lifetime       a table goes away, without a launch, with hdrf_block_delete of its block, with any new
+ *                  recipe for its id (a write or hdrf_recipe_load), with hdrf_reset (and an
+ *                  hdrf_reset_async when it is applied), hdrf_seek_drop and hdrf_close.  It stays valid
+ *                  through hdrf_gc (a live recipe's digests are kept), hdrf_compact (start and stop
+ *                  move, lengths do not) and hdrf_index_resize (entries move verbatim).
+ * hdrf_seek_drop forgets the tables of n ids (unknown ids are ignored); ids == NULL: all of them, and the
+ * store's memory is freed (dropped tables' bytes are not reclaimed one by one: drop all and build again).
+ * hdrf_seek_info_get: what the store holds and what the last hdrf_read_batch* / hdrf_read_range* call did.
+ *
+ * With a table hdrf_read_batch and hdrf_read_range serve a request that names a stored recipe by
+ * block_id from it; a request that carries its own recipe, or whose block has no table, goes the way
+ * described above, and one call may mix both.  The contract above holds, and in addition:
+ *   - only the digests and the containers of the chunks under the range are consulted: a digest absent
+ *     from the index elsewhere in the recipe, or an unreadable container there, does not fail the request;
+ *   - a zero-length request (length == 0 or offset == size) returns 0 without a lookup;
+ *   - HDRF_E_DEVICE also tells that the table and the index disagree on the length of a chunk under the
+ *     range (hdrf_last_error says so).  No public call produces that state deterministically (loading
+ *     a digest that is present is outside hdrf_index_load's contract): the check is a guard;
+ *   - last_rows counts the chunk rows the call's lookups ran over: the whole recipe for a request without
+ *     a table, min(n, clipped length / max(minlen, 1) + 2) for one with a table and a non-empty range,
+ *     where minlen is the smallest length among the recipe's chunks but the last (the chunks strictly
+ *     inside a range are that long at least, and two more are cut by its ends); last_seek_reqs counts
+ *     the requests served from a table. */
+typedef struct {
+    int64_t blocks;          /* tables held */
+    int64_t chunks;          /* ... and the chunks they describe */
+    int64_t bytes;           /* device bytes of the seek store (allocated, whether or not a table uses them) */
+    int64_t last_rows;       /* the last read call: chunk rows its lookups ran over */
+    int64_t last_seek_reqs;  /* ... and requests served from a table */
+} hdrf_seek_info;
+int hdrf_seek_build(hdrf_ctx *ctx, const uint64_t *block_ids, int32_t n, int32_t *result);
+int hdrf_seek_drop(hdrf_ctx *ctx, const uint64_t *block_ids, int32_t n);
+int hdrf_seek_info_get(hdrf_ctx *ctx, hdrf_seek_info *out);
+
+/* Verified ranged reads: hdrf_read_batch / hdrf_read_range as above (with or without a seek table), then,
+ * on the same stream, every chunk that shares a byte with a successful request's range is re-hashed WHOLE
+ * and compared with its recipe digest.  A chunk that lies wholly inside the range is hashed from the
+ * output bytes, which checks the gather as well as the container; the at most two chunks the range cuts
+ * are hashed from their container's bytes (the copy of their served part is not covered).  On a mismatch
+ * the request's result is HDRF_E_CORRUPT and bad_chunk[i] is the lowest failing position IN THE RECIPE
+ * (not in the range); the range's bytes are in the output anyway, and hdrf_last_error names the digest,
+ * the container and the range of the first such request.  bad_chunk[i] = -1 otherwise (n entries;
+ * hdrf_read_range_verified: one).  HDRF_E_INVAL when bad_chunk is NULL. */
+int hdrf_read_batch_verified(hdrf_ctx *ctx, int32_t n, hdrf_read_req *req, int64_t *bad_chunk);
+int64_t hdrf_read_range_verified(hdrf_ctx *ctx, uint64_t block_id, uint64_t offset, uint64_t length, uint8_t *out,
+                                 int64_t cap, int64_t *bad_chunk);
+
 /* The same read on a node-global context (cfg.n_ranks = G > 1): the node's ONE index is
  * partitioned over the ranks, and a container's bytes are spread over the ranks that placed
  * chunks into it, so every rank takes part (hdrf_amd/node.py NodeRank.reconstruct_block; the

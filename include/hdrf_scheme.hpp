@@ -133,6 +133,19 @@ class HipReductionScheme final : public ReductionScheme {
         return read_range(block_id, offset, length);
     }
 
+    // build the seek tables of the stored blocks `ids`, so that ranged reads of them look up only the
+    // chunks under a range instead of the whole recipe: the per-id results (0 or an HDRF_E_* code).  A
+    // table lasts until its block is deleted, rewritten or the context is reset.
+    std::vector<int32_t> prepare_reads(const std::vector<uint64_t> &ids)
+    {
+        std::vector<int32_t> res(ids.size(), 0);
+        const int rc = hdrf_seek_build(ctx_, ids.data(), (int32_t)ids.size(), res.data());
+        bool per_id = false;
+        for (int32_t r : res) per_id |= r == rc;
+        if (rc < 0 && !per_id) check(rc);
+        return res;
+    }
+
     // every index entry whose container is readable re-hashed against its key: the bad chunks
     // (sorted by container, start, digest) and, when st is given, the counts
     std::vector<hdrf_bad_chunk> scrub(int64_t container = -1, hdrf_scrub_stats *st = nullptr)

@@ -7,6 +7,11 @@ with keep_recipes = 1, then
       (the reference's shape: rebuild the block, then seek)
   (d) one 128 MiB block of bytes >= 0x80 (forced cuts: 1,000,001-B chunks), both ways
   (e) (b) at 32 per call for T = 4, 8 and 16 KiB (HDRF_READ_TILE)
+  (f) hdrf_seek_build of every block, 256 ids per call (the blocks' ids in turn), in ms per id
+  (g) (b) and (c) again with the seek tables built: same run, same requests; the table-less legs above run
+      code the tables do not touch.  With each (c) leg, the chunk rows of its last call (hdrf_seek_info's
+      last_rows) and the 16 B per row they take in the read scratch: the row array by the layout's
+      arithmetic, not the scratch's capacity read back (the scratch never shrinks within a run)
 Each leg runs three times; all three times are printed (DESIGN.md reports the last two).  Both paths
 are called through ctypes with their arguments built beforehand, so the times are the C-ABI's.
 
@@ -108,6 +113,38 @@ def main():
     assert np.array_equal(ctx.d2h(out, S), forced), "the forced-cut block through hdrf_read_batch differs"
     timed(f"(d) one forced-cut block ({nch} chunks), hdrf_read_batch", S, lambda: run(one, S))
     timed(f"(d) one forced-cut block ({nch} chunks), hdrf_reconstruct", S, lambda: reconstruct(nb))
+
+    def rows_note(label):
+        info = ctx.seek_info()
+        print(f"    {label}: last call {info['last_seek_reqs']} requests from tables, {info['last_rows']} chunk rows = "
+              f"{info['last_rows'] * 16 / 2**20:.2f} MiB of row scratch", flush=True)
+
+    run(ranged[-1:], R)
+    rows_note("(c) without tables")
+    ids = np.array([i % nb for i in range(READ_MAX_REQS)], np.uint64)
+    res = (ctypes.c_int32 * READ_MAX_REQS)()
+
+    def build_tables():
+        rc = L.hdrf_seek_build(h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), READ_MAX_REQS, res)
+        assert rc == 0 and not any(res), rc
+
+    dts = timed(f"(f) hdrf_seek_build, {READ_MAX_REQS} ids per call", READ_MAX_REQS * S, build_tables)
+    print("    " + "  ".join(f"{dt * 1e3 / READ_MAX_REQS:.3f} ms per 128 MiB block" for dt in dts), flush=True)
+    ctx.seek_drop(None)
+    assert ctx.seek_build(list(range(nb))) == [0] * nb
+    info = ctx.seek_info()
+    print(f"    tables: {info['blocks']} blocks, {info['chunks']} chunks, store {info['bytes'] / 2**20:.0f} MiB", flush=True)
+    run(whole[B if B in whole else 8][:1], S)
+    assert np.array_equal(ctx.d2h(out, S), first), "block 0 through the seek path differs"
+    for per, calls in whole.items():
+        timed(f"(g) as (b) with tables, {per} per call", nb * S, lambda: run(calls, S))
+    timed(f"(g) as (c) with tables, {nr} x 64 KiB ranges, 256 per call", nr * R, lambda: run(ranged, R))
+    rows_note("(c) with tables")
+    b0, off0 = picks[(len(ranged) - 1) * READ_MAX_REQS]
+    reconstruct(b0, out + READ_MAX_REQS * R)
+    assert np.array_equal(ctx.d2h(out, R), ctx.d2h(out + READ_MAX_REQS * R + off0, R)), "a ranged read through the seek path differs"
+    ctx.seek_drop(None)
+    timed("(c) again without tables", nr * R, lambda: run(ranged, R))
 
     if B in whole:
         for kib in (4, 8, 16):
